@@ -20,7 +20,14 @@ driver's form) each rank runs directly.  Envs are sharded (weak scaling, 16 384
 envs per rank, global env ids offset by rank) with no data-path collective;
 value = all ranks' agent-steps ÷ max-over-ranks wall time.
 
-Extra JSON fields:
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline figure
+needs: set up, warm up, time the K steps, print the JSON line.  `--dump-outputs DIR`
+also writes what the last timed step returned (obs, reward, terminated, truncated
+and the drawn actions of rank 0's envs) as DIR/<name>.npy; the rollout is seeded,
+so two builds run with the same arguments are comparable array for array.
+Every other leg below runs only with `--full`.
+
+Extra JSON fields (`--full`):
   pyb           the same rollout under Physics.PYB (the kernel's restatement of
                 Bullet's step, the reference's training default).
   mappo         full MAPPO on the same C3 envs (BASELINE config 3) with the
@@ -97,6 +104,11 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=484, help="timed control steps (default: two MultiHover episodes)")
     p.add_argument("--warmup", type=int, default=20)
+    p.add_argument("--full", action="store_true",
+                   help="also run every other leg (CPU baselines, fp64, PYB, MAPPO, the other configs, rank shapes); "
+                        "without it only the headline rollout is timed and the options of those legs have no effect")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the arrays the last timed step of the headline rollout returned as DIR/<name>.npy")
     p.add_argument("--envs", type=int, default=16384, help="envs per GPU")
     p.add_argument("--drones", type=int, default=8)
     p.add_argument("--act", default="one_d_pid")
@@ -380,11 +392,35 @@ def stagger_episodes(sw, task):
     sw.set_state(L.STATE_ENV, env)
 
 
-def sim_leg(args, ranks, physics="dyn", task="multihover", E=None, D=None, act=None, aux=(), precision=4):
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, rank, arrays):
+    """--dump-outputs: the [E, ...] arrays of one step as path/<name>.npy (float32;
+    float64 stays), rank r > 0 as <name>.rank<r>.npy.  Past 64 MB in all, the same
+    seeded sample of env rows of every array."""
+    os.makedirs(path, exist_ok=True)
+    E = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(a[0].numel() * (8 if a.dtype == torch.float64 else 4) for a in arrays.values())
+    rows = None
+    if E * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(E, DUMP_MAX_BYTES // row_bytes, replace=False))
+        np.save(os.path.join(path, "env_rows.npy" if rank == 0 else f"env_rows.rank{rank}.npy"),
+                rows.astype(np.float64))
+    for name, a in arrays.items():
+        a = a.cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        np.save(os.path.join(path, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"),
+                a if rows is None else a[rows])
+
+
+def sim_leg(args, ranks, physics="dyn", task="multihover", E=None, D=None, act=None, aux=(), precision=4,
+            dump=None):
     """The timed random-policy rollout: exactly `args.steps` control steps of E envs
     per rank, as replays of HIP graphs of step launches (one per rollout-buffer slot).
     Returns (agent-steps/s over all ranks, max-over-ranks seconds, mean step-kernel
-    ms on the launch stream, steps, resets inside the timed window)."""
+    ms on the launch stream, steps, resets inside the timed window).  `dump`: a
+    directory for what the window's last step wrote (dump_outputs)."""
     from gym_pybullet_drones_amd.envs import QuadSwarm
     from gym_pybullet_drones_amd.utils.enums import Physics
     E = args.envs if E is None else E
@@ -467,6 +503,10 @@ def sim_leg(args, ranks, physics="dyn", task="multihover", E=None, D=None, act=N
     assert sw.reset_error() == 0
     assert torch.isfinite(obs_buf).all()
     _, ended1 = sw.episode_log(cap=0)
+    if dump:
+        k = (plan[-1][1] - 1) % slots   # the slot of the window's last step
+        dump_outputs(dump, ranks.rank, {"obs": obs_buf[k], "reward": rew_buf[k], "terminated": te_buf[k],
+                                        "truncated": tr_buf[k], "actions": act_buf[k]})
     del graphs, plan
     sw.close()
     return E * D * ranks.world * args.steps / elapsed, elapsed, kern_ms, args.steps, int(ended1 - ended_r)
@@ -529,13 +569,16 @@ STRONG_SIM = {"C3": ("one_d_pid", "dyn", "multihover", 8, 16384, bytes_per_agent
 
 def leg_plan(args, world):
     """The legs a run of `world` ranks times, in order: (kind, name, scaling, per-rank
-    envs, per-rank mini_batch_size or None).  world 1: the headline, PYB, the MAPPO
+    envs, per-rank mini_batch_size or None).  Without --full: the headline alone.
+    With it, world 1: the headline, PYB, the MAPPO
     legs (C3 at T = 256 and 32, the C4 / C5 / reference-shape trainer configs) and
     the other BASELINE configs' rollouts.  world > 1: the headline and the MAPPO C3
     leg weak-scaled (16 384 envs per rank, as at world 1), the C4 / C5 trainer and
     rollout legs weak-scaled beside them, and §8(e)'s strong partitions of
     configs 3-5 (STRONG_LEGS / STRONG_SIM)."""
     plan = [("sim", "headline", "weak", args.envs, None)]
+    if not args.full:
+        return plan
     if args.fp64:
         plan.append(("sim", "fp64", "weak", args.envs, None))
     if args.pyb:
@@ -797,7 +840,7 @@ def main():
         return
     E, D = args.envs, args.drones
     progress("headline rollout leg")
-    value, elapsed, kern_ms, steps, eps_done = sim_leg(args, ranks, "dyn")
+    value, elapsed, kern_ms, steps, eps_done = sim_leg(args, ranks, "dyn", dump=args.dump_outputs)
     bpas = bytes_per_agent_step(args.act, "multihover", D)
     nbytes = bpas * E * D
     achieved = nbytes / (kern_ms * 1e-3) / 1e9
@@ -865,12 +908,13 @@ def main():
                 configs[name]["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds / 4, c["task"], c["drones"],
                                                              c["act"], c["physics"], c["aux"])
     if rank == 0:
-        cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(args, args.cpu_seconds, extra22=True)
+        cpu = (None if (not args.full or args.no_cpu_baseline or world > 1) else
+               cpu_baseline(args, args.cpu_seconds, extra22=True))
         traffic, traffic_src = pmc_traffic(E, D, args.act)
         line = {
             "metric": METRIC, "value": value, "unit": "agent-steps/s", "n_gpus": world, "steps": steps,
             "warmup": args.warmup, "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": f"MultiHover {D}-drone x {E} envs/GPU, ActionType.{args.act.upper()}, "
                                    "Physics.DYN, random-policy rollout (C3 env config; MAPPO learner in the "
                                    "'mappo' field)",

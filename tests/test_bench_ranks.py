@@ -53,8 +53,9 @@ def test_bench_one_rank_dry_run():
 def test_bench_two_ranks_lists_strong_legs():
     """At N > 1 the bench also times SURVEY §8(e)'s strong partitions of BASELINE
     configs 3-5 (global envs and global minibatch fixed, 1/G per rank), beside the
-    weak-scaled legs; the dry run lists the plan a GPU run of that size executes."""
-    _, line = _run_bench("--gpus", "2", "--dry-run", "--dry-ms", "1", "--steps", "2", "--warmup", "0")
+    weak-scaled legs; the dry run lists the plan a GPU run of that size executes.
+    Those legs belong to `--full`: a plain run plans the headline rollout alone."""
+    _, line = _run_bench("--gpus", "2", "--full", "--dry-run", "--dry-ms", "1", "--steps", "2", "--warmup", "0")
     legs = {(g["kind"], g["name"], g["scaling"]): g for g in line["legs"]}
     for name, envs in (("C3", 16384), ("C4", 8192), ("C5", 8192)):
         m = legs[("mappo", name, "strong")]
@@ -63,12 +64,15 @@ def test_bench_two_ranks_lists_strong_legs():
     assert legs[("mappo", "C3", "weak")]["envs_per_rank"] == 16384   # the weak legs stay, labelled
     assert ("mappo", "C4", "weak") in legs and ("mappo", "C5", "weak") in legs
     assert ("mappo", "ref", "weak") not in legs   # the 1-GPU reference learner shape
-    _, one = _run_bench("--dry-run", "--dry-ms", "1", "--steps", "2", "--warmup", "0")
+    _, one = _run_bench("--full", "--dry-run", "--dry-ms", "1", "--steps", "2", "--warmup", "0")
     assert not any(g["scaling"] == "strong" for g in one["legs"])
     assert ("mappo", "ref", "weak") in {(g["kind"], g["name"], g["scaling"]) for g in one["legs"]}
     # N = 1: the per-rank strong shapes, each timed on one GPU through the exchange path
     assert ("mappo", "rank_shapes", "rank-shape") in {(g["kind"], g["name"], g["scaling"]) for g in one["legs"]}
     assert not any(g["name"] == "rank_shapes" for g in line["legs"])
+    for n in ("1", "2"):
+        _, plain = _run_bench("--gpus", n, "--dry-run", "--dry-ms", "1", "--steps", "2", "--warmup", "0")
+        assert [(g["kind"], g["name"]) for g in plain["legs"]] == [("sim", "headline")]
 
 
 def test_bytes_per_agent_step_matches_survey():
