@@ -222,6 +222,23 @@ int qs_reset_envs(qs_handle* h, const uint8_t* mask, float* obs, void* stream);
 int qs_step(qs_handle* h, const float* actions, const qs_step_out* out,
             void* stream);
 
+/* n consecutive control steps under the random policy (qs_step with actions
+ * = NULL, n times); step j writes outs[j].  The steps run K to a launch, K =
+ * the handle's fusion depth (environment QS_MAX_FUSED_STEPS at qs_create,
+ * 1..16), with the envs' state kept on-chip between the steps of a launch;
+ * every output is bit-identical to n qs_step calls.  Steps share a launch only
+ * while no output range of one overlaps an output range of another, and
+ * handles that run the deferred reset search after each step (MultiHover
+ * layouts whose reset draws can be rejected) take one step per launch.
+ *
+ * qs_step itself joins consecutive random-policy steps in the same way while
+ * its stream is being captured into a graph: a call whose stream's capture
+ * still ends in the kernel node of the previous call, and whose outputs are
+ * disjoint from that node's, extends the node instead of launching.  An event
+ * recorded on the capturing stream between two such steps and waited for by
+ * another stream therefore marks the whole node, later steps included. */
+int qs_step_many(qs_handle* h, int n, const qs_step_out* outs, void* stream);
+
 /* Copy a state block between the handle and `buf` (device pointer).
  * dir = 0: handle → buf (get), dir = 1: buf → handle (set). */
 int qs_state_io(qs_handle* h, int block, void* buf, int dir, void* stream);

@@ -1,7 +1,8 @@
 // quadswarm.hip — host side of the MI355X quadrotor-swarm step: the C-ABI of
 // include/quadswarm.h (handle, state buffers, launches).  The device code is
 // csrc/step_kernel.h; the kernels are instantiated per task family in
-// step_mh.hip / step_spiral.hip / step_generic.hip.
+// step_mh.hip / step_spiral.hip / step_marl.hip (single step) and their
+// *_fused.hip twins (several control steps per launch).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -14,6 +15,9 @@
 
 #include "quadswarm.h"
 #include "step_launch.h"
+#include "step_fuse.h"
+
+static_assert(qs::kFuseMax == qs::kMaxFuse, "step_fuse.h and step_kernel.h disagree on the fusion depth");
 
 namespace qs {
 // Calibration kernel: dword per lane, grid-stride (MI355X_MICROARCH §HBM).
@@ -153,6 +157,14 @@ struct qs_handle {
   uint64_t seed = 0;
   bool reset_done = false;
   std::vector<double> orig_host;
+  // Steps per launch of the synthetic-policy rollout (QS_MAX_FUSED_STEPS, 1 ..
+  // qs::kMaxFuse; 1 = every step its own launch).  `fuse`: the kernel node of a
+  // stream capture that the last qs_step made and the next one may grow
+  // (step_fuse.h), with the launch parameters the node holds.
+  int fuse_depth = 1;
+  qs::FuseGroup fuse;
+  qs::ParamsMany<float> fuse_pf;
+  qs::ParamsMany<double> fuse_pd;
 };
 
 // Envs per one-wave workgroup: ⌊64/D⌋, a launch parameter (P.EPB).  A dev build
@@ -221,21 +233,50 @@ static int lds_plan(const qs_dims& d, int epb, int resident, int* stage_rows, si
   return QS_OK;
 }
 
-template <class T> static int launch(qs_handle* h, qs::Params<T>& P, hipStream_t st) {
+// What a launch ran (or, select_only, would run): a graph kernel node's fields.
+struct LaunchInfo {
+  const void* fn = nullptr;
+  int grid = 0;
+  size_t lds = 0;
+};
+
+// Grid, LDS plan (P.stage_rows) and the kernel of a launch; FUSE = 1: the
+// multi-step instance over P.io[0 .. P.nsteps-1] (MODE_STEP, no trainer actions,
+// no deferred reset queue: the callers see to that).  select_only: no launch.
+template <class T, int FUSE>
+static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t st, LaunchInfo* info, bool select_only) {
   const int grid = (P.E + P.EPB - 1) / P.EPB;
   size_t lds = 0;
   if (lds_plan(h->dims, P.EPB, (grid + h->num_cu - 1) / h->num_cu, &P.stage_rows, &lds) != QS_OK)
     return fail(QS_E_INVALID, "launch: action history does not fit in LDS (ctrl_freq too high)");
   const qs_spec& s = h->spec;
+  const void* fn = nullptr;
   bool ok;
   if (s.task == QS_TASK_MULTIHOVER)
-    ok = qs::launch_task<T, QS_TASK_MULTIHOVER>(s.act_type, grid, lds, st, P, s.ctrl_freq, s.pyb_freq, s.physics);
+    ok = qs::launch_task<T, QS_TASK_MULTIHOVER, FUSE>(s.act_type, grid, lds, st, P, s.ctrl_freq, s.pyb_freq, s.physics, &fn,
+                                                      select_only);
   else if (s.task == QS_TASK_SPIRAL)
-    ok = qs::launch_task<T, QS_TASK_SPIRAL>(s.act_type, grid, lds, st, P, s.ctrl_freq, s.pyb_freq, s.physics);
+    ok = qs::launch_task<T, QS_TASK_SPIRAL, FUSE>(s.act_type, grid, lds, st, P, s.ctrl_freq, s.pyb_freq, s.physics, &fn,
+                                                  select_only);
   else
-    ok = qs::launch_task<T, qs::kTaskMarl>(s.act_type, grid, lds, st, P, s.ctrl_freq, s.pyb_freq, s.physics);
+    ok = qs::launch_task<T, qs::kTaskMarl, FUSE>(s.act_type, grid, lds, st, P, s.ctrl_freq, s.pyb_freq, s.physics, &fn,
+                                                 select_only);
   if (!ok) return fail(QS_E_INVALID, "launch: bad act_type");
+  if (info) { info->fn = fn; info->grid = grid; info->lds = lds; }
+  if (select_only) return QS_OK;
   HIP_TRY(hipGetLastError());
+  return QS_OK;
+}
+
+// A launch of P.nsteps (>= 2) control steps.
+template <class T> static int launch_many(qs_handle* h, qs::ParamsMany<T>& P, hipStream_t st, LaunchInfo* info = nullptr,
+                                          bool select_only = false) {
+  return launch_kernel<T, 1>(h, P, st, info, select_only);
+}
+
+template <class T> static int launch(qs_handle* h, qs::Params<T>& P, hipStream_t st, LaunchInfo* info = nullptr) {
+  const int rc = launch_kernel<T, 0>(h, P, st, info, false);
+  if (rc != QS_OK) return rc;
   if (P.reset_queue) {   // the envs whose try 0 was rejected (usually none)
     // Workgroups claim chunks of the queued envs' tries dynamically; kQueueWG
     // workgroups for the queue, then one per kPreEnvs envs (up to 4 096 envs,
@@ -272,10 +313,157 @@ static int check_consts() {
   return QS_OK;
 }
 
+// ---------------------------------------------------------------- stepping
+template <class T> static qs::ParamsMany<T>& fuse_params(qs_handle* h) {
+  if constexpr (sizeof(T) == 8) return h->fuse_pd;
+  else return h->fuse_pf;
+}
+template <class T> static qs::StepIO<T> to_io(const qs_step_out& o) {
+  return qs::StepIO<T>{o.obs, (T*)o.reward, o.terminated, o.truncated, o.terminal_obs, o.reasons, o.actions_out};
+}
+static qs::FuseOuts to_outs(const qs_step_out& o) {
+  return qs::FuseOuts{{o.obs, o.reward, o.terminated, o.truncated, o.terminal_obs, o.reasons, o.actions_out}};
+}
+// bytes a step writes through each qs_step_out pointer (to_outs order)
+static void out_sizes(const qs_handle* h, size_t b[qs::kFuseOuts]) {
+  const qs_dims& d = h->dims;
+  const size_t N = (size_t)d.num_agents, E = (size_t)d.num_envs, row = (size_t)d.obs_dim * sizeof(float);
+  b[0] = N * row; b[1] = E * (size_t)d.precision; b[2] = E; b[3] = E; b[4] = N * row; b[5] = N;
+  b[6] = N * (size_t)d.act_dim * sizeof(float);
+}
+template <class T> static void single_step_params(const qs_handle* h, qs::Params<T>& P, const float* actions,
+                                                  const qs_step_out& o) {
+  fill_params(h, P);
+  P.mode = qs::MODE_STEP;
+  P.act_in = actions; P.obs = o.obs; P.rew = (T*)o.reward; P.term = o.terminated; P.trunc = o.truncated;
+  P.tobs = o.terminal_obs; P.reasons = o.reasons; P.act_out = o.actions_out;
+}
+
+struct CaptureState {
+  bool active = false;
+  unsigned long long id = 0;
+  const hipGraphNode_t* deps = nullptr;
+  size_t ndeps = 0;
+};
+// The capture `st` is in, if any; a failed query counts as none.
+static CaptureState capture_state(hipStream_t st) {
+  CaptureState c;
+  hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+  hipGraph_t graph = nullptr;
+  if (hipStreamGetCaptureInfo_v2(st, &status, &c.id, &graph, &c.deps, &c.ndeps) != hipSuccess) {
+    (void)hipGetLastError();
+    return CaptureState{};
+  }
+  c.active = status == hipStreamCaptureStatusActive;
+  return c;
+}
+
+// qs_step on a capturing stream, synthetic policy: if the stream's capture still
+// ends in the kernel node the previous qs_step made (h->fuse) and nothing else
+// depends on that node, this step joins it: the node becomes the multi-step
+// kernel over one more output set, and nothing is launched.  false: the caller
+// takes the single launch (any doubt, any refusal of the runtime).
+template <class T> static bool try_coalesce(qs_handle* h, const qs_step_out& o, hipStream_t st) {
+  qs::FuseGroup& g = h->fuse;
+  const CaptureState c = capture_state(st);
+  if (!c.active || !g.same_capture(c.id, (void*)st)) return false;   // (ids first: the node of an ended capture may be gone)
+  hipGraphNode_t node = (hipGraphNode_t)g.node;
+  if (c.ndeps != 1 || c.deps[0] != node) return false;
+  size_t dependents = 0;
+  if (hipGraphNodeGetDependentNodes(node, nullptr, &dependents) != hipSuccess) { (void)hipGetLastError(); return false; }
+  if (dependents != 0) return false;
+  const qs::FuseOuts fo = to_outs(o);
+  if (!g.can_append(fo, h->fuse_depth)) return false;
+  qs::ParamsMany<T> P = fuse_params<T>(h);
+  P.io[g.count] = to_io<T>(o);
+  P.nsteps = g.count + 1;
+  LaunchInfo li;
+  if (launch_many(h, P, st, &li, /*select_only=*/true) != QS_OK || !li.fn) return false;
+  hipKernelNodeParams np;
+  std::memset(&np, 0, sizeof(np));
+  void* args[1] = {&P};
+  np.func = const_cast<void*>(li.fn);
+  np.gridDim = dim3((unsigned)li.grid);
+  np.blockDim = dim3(qs::kBlock);
+  np.sharedMemBytes = (unsigned)li.lds;
+  np.kernelParams = args;   // (the runtime copies the arguments during the call)
+  if (hipGraphKernelNodeSetParams(node, &np) != hipSuccess) { (void)hipGetLastError(); return false; }
+  fuse_params<T>(h) = P;
+  g.append(fo);
+  return true;
+}
+
+// After a single-step synthetic-policy launch on a capturing stream: remember
+// the kernel node it became, so that the next qs_step may join it.
+template <class T> static void note_capture(qs_handle* h, const qs::Params<T>& P, const qs_step_out& o, hipStream_t st,
+                                            const LaunchInfo& li) {
+  const CaptureState c = capture_state(st);
+  if (!c.active || c.ndeps != 1) return;
+  hipGraphNodeType ty;
+  hipKernelNodeParams np;
+  if (hipGraphNodeGetType(c.deps[0], &ty) != hipSuccess || ty != hipGraphNodeTypeKernel ||
+      hipGraphKernelNodeGetParams(c.deps[0], &np) != hipSuccess) {
+    (void)hipGetLastError();
+    return;
+  }
+  if (np.func != li.fn) return;   // not the launch just made
+  size_t sizes[qs::kFuseOuts];
+  out_sizes(h, sizes);
+  h->fuse.begin(sizes, to_outs(o), c.id, (void*)st, (void*)c.deps[0]);
+  qs::ParamsMany<T>& F = fuse_params<T>(h);
+  std::memset(&F, 0, sizeof(F));
+  static_cast<qs::Params<T>&>(F) = P;
+  F.io[0] = to_io<T>(o);
+  F.nsteps = 1;
+}
+
+template <class T> static int step_impl(qs_handle* h, const float* actions, const qs_step_out& o, hipStream_t st) {
+  // steps that may share a launch: synthetic policy, no search launch between two steps
+  const bool fusable = h->fuse_depth > 1 && actions == nullptr && h->rq == nullptr;
+  if (fusable && h->fuse.live && try_coalesce<T>(h, o, st)) return QS_OK;
+  h->fuse.forget();
+  qs::Params<T> P;
+  single_step_params(h, P, actions, o);
+  LaunchInfo li;
+  const int rc = launch(h, P, st, &li);
+  if (rc == QS_OK && fusable) note_capture<T>(h, P, o, st, li);
+  return rc;
+}
+
+template <class T> static int step_many_impl(qs_handle* h, int n, const qs_step_out* outs, hipStream_t st) {
+  const int depth = h->rq ? 1 : h->fuse_depth;   // the search launch sits between two steps of an env
+  size_t sizes[qs::kFuseOuts];
+  out_sizes(h, sizes);
+  for (int j = 0; j < n;) {
+    // the longest run of steps from j whose outputs are pairwise disjoint, up to the depth
+    qs::FuseGroup g;
+    g.begin(sizes, to_outs(outs[j]));
+    while (j + g.count < n && g.can_append(to_outs(outs[j + g.count]), depth)) g.append(to_outs(outs[j + g.count]));
+    qs::ParamsMany<T> P;
+    std::memset(&P, 0, sizeof(P));
+    single_step_params<T>(h, P, nullptr, outs[j]);
+    int rc;
+    if (g.count > 1) {
+      P.nsteps = g.count;
+      for (int k = 0; k < g.count; ++k) P.io[k] = to_io<T>(outs[j + k]);
+      rc = launch_many(h, P, st);
+    } else {
+      rc = launch<T>(h, P, st);
+    }
+    if (rc != QS_OK) return rc;
+    j += g.count;
+  }
+  return QS_OK;
+}
+
 extern "C" {
 
 const char* qs_last_error(void) { return g_err.c_str(); }
 int qs_abi_version(void) { return QS_ABI_VERSION; }
+
+// Default fusion depth of the synthetic-policy rollout (QS_MAX_FUSED_STEPS
+// overrides it): the fastest of 4 / 8 / 16 on the C3 bench (profiles/step_fusion_ab.json).
+static constexpr int kDefaultFusedSteps = 16;
 
 int qs_create(const qs_spec* spec, int device, qs_handle** out) {
   if (!spec || !out) return fail(QS_E_INVALID, "qs_create: null argument");
@@ -319,6 +507,12 @@ int qs_create(const qs_spec* spec, int device, qs_handle** out) {
   HIP_TRY(hipSetDevice(device));
   auto* h = new (std::nothrow) qs_handle();
   if (!h) return fail(QS_E_NOMEM, "qs_create: host allocation failed");
+  h->fuse_depth = kDefaultFusedSteps;
+  if (const char* v = getenv("QS_MAX_FUSED_STEPS")) {   // read once, here
+    char* end = nullptr;
+    const long k = std::strtol(v, &end, 10);
+    if (end != v) h->fuse_depth = (int)std::min<long>(std::max<long>(k, 1), qs::kMaxFuse);
+  }
   h->spec = s;
   h->spec.initial_xyzs = nullptr;
   h->device = device;
@@ -442,6 +636,7 @@ int qs_get_dims(const qs_handle* h, qs_dims* out) {
 int qs_reset(qs_handle* h, uint64_t seed, float* obs, void* stream) {
   if (!h) return fail(QS_E_INVALID, "qs_reset: null handle");
   hipStream_t st = (hipStream_t)stream;
+  h->fuse.forget();
   const qs_dims& d = h->dims;
   const size_t N = d.num_agents, rs = d.precision;
   HIP_TRY(hipSetDevice(h->device));
@@ -470,6 +665,7 @@ int qs_reset_envs(qs_handle* h, const uint8_t* mask, float* obs, void* stream) {
   if (!h) return fail(QS_E_INVALID, "qs_reset_envs: null handle");
   if (!h->reset_done) return fail(QS_E_STATE, "qs_reset_envs: call qs_reset first");
   hipStream_t st = (hipStream_t)stream;
+  h->fuse.forget();
   if (h->dims.precision == 8) {
     qs::Params<double> P; fill_params(h, P); P.mode = qs::MODE_RESET_MASK; P.reset_mask = mask; P.obs = obs;
     return launch(h, P, st);
@@ -484,16 +680,18 @@ int qs_step(qs_handle* h, const float* actions, const qs_step_out* out, void* st
   hipStream_t st = (hipStream_t)stream;
   qs_step_out o{};
   if (out) o = *out;
-  if (h->dims.precision == 8) {
-    qs::Params<double> P; fill_params(h, P); P.mode = qs::MODE_STEP;
-    P.act_in = actions; P.obs = o.obs; P.rew = (double*)o.reward; P.term = o.terminated; P.trunc = o.truncated;
-    P.tobs = o.terminal_obs; P.reasons = o.reasons; P.act_out = o.actions_out;
-    return launch(h, P, st);
-  }
-  qs::Params<float> P; fill_params(h, P); P.mode = qs::MODE_STEP;
-  P.act_in = actions; P.obs = o.obs; P.rew = (float*)o.reward; P.term = o.terminated; P.trunc = o.truncated;
-  P.tobs = o.terminal_obs; P.reasons = o.reasons; P.act_out = o.actions_out;
-  return launch(h, P, st);
+  if (h->dims.precision == 8) return step_impl<double>(h, actions, o, st);
+  return step_impl<float>(h, actions, o, st);
+}
+
+int qs_step_many(qs_handle* h, int n, const qs_step_out* outs, void* stream) {
+  if (!h) return fail(QS_E_INVALID, "qs_step_many: null handle");
+  if (n < 0 || (n > 0 && !outs)) return fail(QS_E_INVALID, "qs_step_many: bad argument");
+  if (!h->reset_done) return fail(QS_E_STATE, "qs_step_many: call qs_reset first");
+  h->fuse.forget();
+  hipStream_t st = (hipStream_t)stream;
+  if (h->dims.precision == 8) return step_many_impl<double>(h, n, outs, st);
+  return step_many_impl<float>(h, n, outs, st);
 }
 
 // qs_state_io's view of the per-env records: counters as [QS_ENV_FIELDS][E]
@@ -525,6 +723,7 @@ __global__ void env_io_kernel(int32_t* rec, void* ext, int E, bool counters, boo
 int qs_state_io(qs_handle* h, int block, void* buf, int dir, void* stream) {
   if (!h || !buf) return fail(QS_E_INVALID, "qs_state_io: null argument");
   hipStream_t st = (hipStream_t)stream;
+  h->fuse.forget();
   const qs_dims& d = h->dims;
   void* src = nullptr;
   size_t bytes = 0;
@@ -553,6 +752,7 @@ int qs_episode_log(qs_handle* h, qs_episode_rec* dst, int64_t cap, int64_t* tota
   if (!h || !total) return fail(QS_E_INVALID, "qs_episode_log: null argument");
   if (written) *written = 0;
   hipStream_t st = (hipStream_t)stream;
+  h->fuse.forget();
   HIP_TRY(hipSetDevice(h->device));
   const int E = h->dims.num_envs, R = h->log_per_env;
   const unsigned grid = (unsigned)((E + 255) / 256);
@@ -616,6 +816,7 @@ int qs_episode_log(qs_handle* h, qs_episode_rec* dst, int64_t cap, int64_t* tota
 
 int qs_reset_error(qs_handle* h, int* out) {
   if (!h || !out) return fail(QS_E_INVALID, "qs_reset_error: null argument");
+  h->fuse.forget();
   HIP_TRY(hipMemcpy(out, h->err, sizeof(int), hipMemcpyDeviceToHost));
   return QS_OK;
 }

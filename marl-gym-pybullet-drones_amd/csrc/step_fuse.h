@@ -1,0 +1,89 @@
+// step_fuse.h — host-side bookkeeping of a multi-step launch (plain C++, no HIP).
+//
+// A multi-step launch of step_kernel runs up to kFuseMax consecutive control
+// steps of the same envs; step j writes through its own set of output
+// pointers.  Waves of one launch are at different steps at the same moment, so
+// no output range of a step may overlap an output range of another step of the
+// same launch (within one step the caller's buffers are what they are for a
+// single step).  FuseGroup collects the steps of one launch under that rule;
+// qs_step uses it to grow a kernel node of a stream capture (capture id,
+// stream and node say which), qs_step_many to cut its steps into launches.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+namespace qs {
+
+constexpr int kFuseMax = 16;    // = kMaxFuse (step_kernel.h), checked in quadswarm.hip
+constexpr int kFuseOuts = 7;    // obs, reward, terminated, truncated, terminal_obs, reasons, actions_out
+
+struct FuseOuts {
+  const void* p[kFuseOuts];
+};
+
+struct FuseGroup {
+  bool live = false;
+  unsigned long long capture_id = 0;   // the stream capture the node belongs to
+  void* stream = nullptr;
+  void* node = nullptr;                // the kernel node that holds `count` steps
+  int count = 0;
+  size_t bytes[kFuseOuts] = {0, 0, 0, 0, 0, 0, 0};   // size of each output a step writes
+  FuseOuts outs[kFuseMax];
+
+  void forget() {
+    live = false;
+    node = nullptr;
+    stream = nullptr;
+    count = 0;
+  }
+
+  // A new group whose first step writes `o`.
+  void begin(const size_t sizes[kFuseOuts], const FuseOuts& o, unsigned long long id = 0, void* st = nullptr,
+             void* nd = nullptr) {
+    for (int i = 0; i < kFuseOuts; ++i) bytes[i] = sizes[i];
+    outs[0] = o;
+    count = 1;
+    capture_id = id;
+    stream = st;
+    node = nd;
+    live = true;
+  }
+
+  static bool overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+  }
+
+  // Every non-null output range of `o` is disjoint from every non-null output
+  // range of the steps already in the group.
+  bool distinct(const FuseOuts& o) const {
+    for (int i = 0; i < kFuseOuts; ++i) {
+      if (!o.p[i]) continue;
+      for (int s = 0; s < count; ++s)
+        for (int j = 0; j < kFuseOuts; ++j)
+          if (outs[s].p[j] && overlap(o.p[i], bytes[i], outs[s].p[j], bytes[j])) return false;
+    }
+    return true;
+  }
+
+  // May a further step with outputs `o` join, at fusion depth `depth`?
+  bool can_append(const FuseOuts& o, int depth) const {
+    const int cap = depth < kFuseMax ? depth : kFuseMax;
+    return live && count >= 1 && count < cap && distinct(o);
+  }
+
+  // The same for the node of a capture: the caller's stream must still be in
+  // the capture that made the node.  (Compared before the node is touched: a
+  // node of an ended capture may be gone.)
+  bool same_capture(unsigned long long id, const void* st) const {
+    return live && node != nullptr && id == capture_id && st == stream;
+  }
+
+  void append(const FuseOuts& o) {
+    outs[count] = o;
+    count += 1;
+  }
+};
+
+}  // namespace qs

@@ -244,6 +244,19 @@ __device__ __forceinline__ U4 philox(U4 c, uint32_t k0, uint32_t k1) {
 template <class T> __device__ __forceinline__ T u01(uint32_t x) { return T(x >> 8) * T(1.0 / 16777216.0); }
 
 // -------------------------------------------------------------- parameters
+// Outputs of one control step (all optional).  A multi-step launch (step_kernel
+// FUSE) writes step j of the launch through ParamsMany::io[j].
+constexpr int kMaxFuse = 16;
+template <class T> struct StepIO {
+  float* obs;
+  T* rew;
+  uint8_t* term;
+  uint8_t* trunc;
+  float* tobs;
+  uint8_t* reasons;
+  float* act_out;
+};
+
 template <class T> struct Params {
   // sizes
   int E, D, N, O, H, S, EPB;
@@ -280,6 +293,15 @@ template <class T> struct Params {
   uint8_t* reasons;
   float* act_out;
 };
+// Arguments of the multi-step instances (step_kernel FUSE): the per-step I/O
+// members above are unused, step j writes io[j].  A type of its own, so that the
+// single-step kernels keep their argument block (with the 900 bytes of io[] in
+// it they compiled to different code).
+template <class T> struct ParamsMany : Params<T> {
+  int nsteps;
+  StepIO<T> io[kMaxFuse];
+};
+template <class T, int FUSE> using KernelParams = std::conditional_t<FUSE != 0, ParamsMany<T>, Params<T>>;
 
 // ---------------------------------------------------- conversions (external)
 // pybullet getMatrixFromQuaternion = btMatrix3x3::setRotation (s = 2/|q|²).
@@ -714,6 +736,9 @@ __device__ __forceinline__ float downwash16(float px, float py, float pz) {
 }
 
 
+template <class T> __device__ __forceinline__ int launch_steps(const Params<T>&) { return 1; }
+template <class T> __device__ __forceinline__ int launch_steps(const ParamsMany<T>& P) { return P.nsteps; }
+
 // ---------------------------------------------------------------- the step
 // TASK (qs_task) and ACT (qs_action_type) are compile-time: each launch runs
 // a kernel with only its own task's obs/reward code and its own action
@@ -728,9 +753,20 @@ __device__ __forceinline__ float downwash16(float px, float py, float pz) {
 // only (C5's PYB_DW), kept on the fp32 fast substep; 2 = any combination
 // through the general substep (the P.aux bits decide at run time); 3 = the
 // same for DroneModel.CF2P (QS_FLAG_CF2P).
-template <class T, int TASK, int ACT, int CF, int PHYS, int AUXM>
-__global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
+// FUSE = 1: P.nsteps consecutive synthetic-policy control steps (MODE_STEP, no
+// trainer actions, no deferred reset queue) of the same envs in one launch.  The
+// loads run once, then every step does the single step's operations in the
+// single step's order on values that stay in registers (state, PID integrators,
+// target, env counters, the action-history ring); step j's outputs go to
+// P.io[j] (ParamsMany), the new action to its global ring slot (store only) and
+// into the register / LDS ring, and the state is stored once after the last
+// step.  Bit-identical to P.nsteps launches of the FUSE = 0 instance, which
+// compiles to the code it had before the flag existed (no loop is emitted for it).
+template <class T, int TASK, int ACT, int CF, int PHYS, int AUXM, int FUSE = 0>
+__global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   using F = M<T>;
+  constexpr bool kFuse = FUSE != 0;
+  const int mode = kFuse ? (int)MODE_STEP : P.mode;
   constexpr bool kP = AUXM == 3;   // DroneModel.CF2P
   using MD = Model<kP>;
   constexpr int A = Act<ACT>::A;
@@ -777,7 +813,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
   const v2u_t c23 = __builtin_amdgcn_raw_buffer_load_b64(env_r, (int)ev, 8, 0);
   int32_t step_counter = (int32_t)c01.x, episode = (int32_t)c01.y;
   int32_t total = (int32_t)c23.x, ep_len = (int32_t)c23.y;
-  const double ep_ret0 = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(env_r, (int)ev, kEnvRetWord * 4, 0));
+  double ep_ret0 = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(env_r, (int)ev, kEnvRetWord * 4, 0));
   const v2u_t c67 = __builtin_amdgcn_raw_buffer_load_b64(env_r, (int)ev, kEnvLogWord * 4, 0);
   const int32_t log_n0 = (int32_t)c67.x;
   // the precomputed search (kPreFound encoding): the next episode's try, or the
@@ -812,7 +848,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
   // trainer actions (absent: zero-size descriptor), episode return, reset mask
   float act_in[A];
   {
-    const __amdgpu_buffer_rsrc_t r = rsrc(P.act_in, P.act_in ? (unsigned)N * A * 4u : 0u);
+    const __amdgpu_buffer_rsrc_t r = rsrc(P.act_in, (!kFuse && P.act_in) ? (unsigned)N * A * 4u : 0u);
     const unsigned v = valid ? (unsigned)a * A * 4u : kOOB;
 #pragma unroll
     for (int k = 0; k < A; ++k) act_in[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)(v + 4u * k), 0, 0));
@@ -869,7 +905,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
     return A == 3 ? hist_pref[(sl * 3 + k) * kBlock + tid] : hist_pref[(sl * kBlock + tid) * A + k];
   };
   // history ring head: this step's action goes to slot total % H
-  const int wslot = total % H;
+  int wslot = total % H;
   // kinematic state + last_clipped_action (BaseAviary.py:509-519, 560)
   auto store_kin = [&]() {
 #pragma unroll
@@ -889,14 +925,32 @@ __global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
   int32_t log_n = log_n0;        // episodes logged by this env
   bool done_env = false;
   int obs_sc = step_counter;   // step_counter seen by _computeObs (before BaseAviary.py:382)
+  bool do_reset = false;
+  bool any_reset = false;      // FUSE: some step of this launch reset the env (its target is stored at the end)
 
   float cur_act[A];            // this step's action (newest history entry)
 #pragma unroll
   for (int k = 0; k < A; ++k) cur_act[k] = 0.f;
   QS_STAMP_SINK(pos[0] + q[3] + pid[0] + tgt[0] + (T)total);
+  // FUSE: every load has landed before the loop, which issues none (its stores
+  // are never waited for: nothing reads what they write).
+  if constexpr (kFuse) wait_vm0();
+  // (a do-while whose condition is the constant false without FUSE: no loop
+  // is emitted for the single-step instances)
+  int ks = 0;
+#pragma clang loop unroll(disable)
+  do {
+  StepIO<T> io{P.obs, P.rew, P.term, P.trunc, P.tobs, P.reasons, P.act_out};
+  if constexpr (kFuse) io = P.io[ks];
+  if constexpr (kFuse) {   // what the next single-step launch would read back from its loads
+    ep_ret0 = ep_ret_out;
+    ep_len = ep_len_out;
+    obs_sc = step_counter;
+    done_env = false;
+  }
   // ---------------- action (trainer-provided or synthetic random policy)
-  if (P.mode == MODE_STEP) {
-    if (P.act_in) {
+  if (mode == MODE_STEP) {
+    if (!kFuse && P.act_in) {
 #pragma unroll
       for (int k = 0; k < A; ++k) cur_act[k] = act_in[k];
     } else {
@@ -907,7 +961,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
     }
   }
   QS_STAMP(1);
-  if (P.mode == MODE_STEP) {
+  if (mode == MODE_STEP) {
     const float* act = cur_act;
     // ---------------- _preprocessAction (BaseRLAviary.py:188-239)
     T rpm[4] = {0, 0, 0, 0};
@@ -946,14 +1000,14 @@ __global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
     // wait is held up by the stores (see wait_vm0).  The compiler's own waits
     // let the action draw and the PID start as soon as the state loads land,
     // with the history LDS-DMA (issued last) still streaming.
-    wait_vm0();
+    if constexpr (!kFuse) wait_vm0();
     if (valid) {
       // one vector store per lane for the A components (a wave writes whole
       // lines; per-component dword stores left 16-B-strided partial lines)
-      if (P.act_out) store_act<A>(P.act_out + (size_t)a * A, act);
+      if (io.act_out) store_act<A>(io.act_out + (size_t)a * A, act);
       // action_buffer.append(action) (BaseRLAviary.py:187): ring slot total % H
       store_act<A>(P.hist + ((size_t)wslot * N + a) * A, act);
-      if constexpr (kPid) {   // PID integrators are final: store now, drains under the substeps
+      if constexpr (kPid && !kFuse) {   // PID integrators are final: store now, drains under the substeps
 #pragma unroll
         for (int i = 0; i < 9; ++i) SA.st(QS_F_PID_INT_POS + i, pid[i]);
       }
@@ -1349,7 +1403,9 @@ __global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
     total += 1;
     // Kinematic state is final unless this env auto-resets (rewritten below):
     // store now so the writes drain under the reward / obs phases.
-    if (valid) store_kin();
+    if constexpr (!kFuse) {
+      if (valid) store_kin();
+    }
     QS_STAMP(3);
 
     // ---------------- reward / termination per drone
@@ -1430,9 +1486,9 @@ __global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
         te = P.task == QS_TASK_MEETUP && meetup_met<T>(&s.cand[tid], D);
         tr = any != 0 || tr;   // (no termination-reason strings for these tasks)
       }
-      if (P.rew) P.rew[e] = r;
-      if (P.term) P.term[e] = te;
-      if (P.trunc) P.trunc[e] = tr;
+      if (io.rew) io.rew[e] = r;
+      if (io.term) io.term[e] = te;
+      if (io.trunc) io.trunc[e] = tr;
       ret = ep_ret0 + (double)r;
       len = ep_len + 1;
       dn = te || tr;
@@ -1450,11 +1506,11 @@ __global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
       P.log[(size_t)e * P.log_per_env + (unsigned)log_n % (unsigned)P.log_per_env] = rec;
       log_n = log_n + 1;
     }
-    if (P.reasons && valid) P.reasons[a] = kMarl ? 0 : bits;
+    if (io.reasons && valid) io.reasons[a] = kMarl ? 0 : bits;
     step_counter += S;   // BaseAviary.py:382
     __syncthreads();
     done_env = valid && s.done[lenv];
-  } else if (P.mode == MODE_RESET_ALL) {
+  } else if (mode == MODE_RESET_ALL) {
     wait_vm0();
     // qs_reset: every env starts episode 0 (history is zero after qs_reset)
     done_env = valid;
@@ -1477,7 +1533,8 @@ __global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
     done_env = valid && masked;
   }
   // worker.step_env resets on done unless this is a single-env facade
-  const bool do_reset = done_env && !(P.mode == MODE_STEP && (P.flags & QS_FLAG_NO_AUTORESET));
+  do_reset = done_env && !(mode == MODE_STEP && (P.flags & QS_FLAG_NO_AUTORESET));
+  any_reset = any_reset || do_reset;
 
   // ---------------- obs writer (BaseRLAviary._computeObs + Spiral extras)
   auto write_obs_row = [&](float* o, int sc) {
@@ -1487,7 +1544,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
     }
     // history, oldest first: ring slots base .. base+H-2 (mod H), then this
     // step's action (BaseRLAviary.py:317-318)
-    const int base = P.mode == MODE_STEP ? wslot + 1 : wslot;
+    const int base = mode == MODE_STEP ? wslot + 1 : wslot;
     if constexpr (CF != 0) {   // register ring: slot sl goes to column (sl - base) mod H
 #pragma unroll
       for (int sl = 0; sl < HR; ++sl) {
@@ -1523,7 +1580,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
   };
 
   QS_STAMP(4);
-  if (valid && done_env && P.mode == MODE_STEP && P.tobs) write_obs_row(P.tobs + (size_t)a * O, obs_sc);
+  if (valid && done_env && mode == MODE_STEP && io.tobs) write_obs_row(io.tobs + (size_t)a * O, obs_sc);
 
   // ---------------- auto-reset (worker.step_env → env.reset)
   s.any = 0;
@@ -1532,7 +1589,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
   __syncthreads();
   if (s.any) {
     if (d == 0 && lenv < P.EPB) s.need[lenv] = do_reset ? 1 : 0;
-    if (P.mode != MODE_RESET_ALL && do_reset) episode += 1;
+    if (mode != MODE_RESET_ALL && do_reset) episode += 1;
     T init[3] = {orig[0], orig[1], orig[2]};
     if constexpr (kHover) {
       if (P.reject_free) {   // workgroup-uniform: no pair test, no barriers
@@ -1541,7 +1598,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
       } else {
         // The next episode's first accepted try, when reset_search_kernel's
         // precompute has found it ahead of time (reset_pre, tagged with this episode)
-        const bool pre_ok = P.reset_pre && P.mode != MODE_RESET_ALL && do_reset && pre0 < 0 &&
+        const bool pre_ok = P.reset_pre && mode != MODE_RESET_ALL && do_reset && pre0 < 0 &&
                             pre_tag_is(pre0, (uint32_t)episode);
         if (pre_ok) reset_candidate(P, orig, d, (uint32_t)pre0 & 0xffffffu, genv, (uint32_t)episode, init[0], init[1], init[2]);
         // Phase 1: every other group tries index 0 for its own env.
@@ -1634,15 +1691,15 @@ __global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
 
   QS_STAMP(5);
   // ---------------- obs output
-  if (P.obs) {
-    if (P.mode == MODE_RESET_MASK) {
-      if (valid && do_reset) write_obs_row(P.obs + (size_t)a * O, obs_sc);
+  if (io.obs) {
+    if (mode == MODE_RESET_MASK) {
+      if (valid && do_reset) write_obs_row(io.obs + (size_t)a * O, obs_sc);
     } else {
       // The block's obs rows are one contiguous span of HBM: build them in LDS
       // and store the span with 16-byte coalesced stores (a per-lane row store
       // touches 64 lines per wave instruction and doubled the write traffic).
       const int nvalid = [&] { const int e0 = blockIdx.x * P.EPB; return min(P.EPB, P.E - e0) * D; }();
-      float* const blk = P.obs + (size_t)blockIdx.x * P.EPB * D * O;
+      float* const blk = io.obs + (size_t)blockIdx.x * P.EPB * D * O;
       for (int p0 = 0; p0 < nvalid; p0 += P.stage_rows) {   // block-uniform
         const int p1 = min(nvalid, p0 + P.stage_rows);
         if (tid >= p0 && tid < p1) write_obs_row(stage + (tid - p0) * O, obs_sc);
@@ -1667,6 +1724,24 @@ __global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
     }
   }
   QS_STAMP(6);
+  if constexpr (kFuse) {
+    // the next step's view of the ring: this step's action takes slot wslot
+    // (the launches' `total % H`; total advances by one per step)
+    if constexpr (CF != 0) {
+#pragma unroll
+      for (int sl = 0; sl < HR; ++sl)
+#pragma unroll
+        for (int k = 0; k < A; ++k) hreg[sl][k] = sl == wslot ? cur_act[k] : hreg[sl][k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < A; ++k) {
+        if constexpr (A == 3) hist_pref[(wslot * 3 + k) * kBlock + tid] = cur_act[k];
+        else hist_pref[(wslot * kBlock + tid) * A + k] = cur_act[k];
+      }
+    }
+    wslot = wslot + 1 == H ? 0 : wslot + 1;
+  }
+  } while (kFuse && ++ks < launch_steps(P));   // control steps of this launch
   // ---------------- per-env records: staged in LDS, stored as one span
   if (valid && d == 0) {
     int32_t* r = &s.rec[lenv * kEnvRec];
@@ -1686,6 +1761,20 @@ __global__ void __launch_bounds__(kBlock) step_kernel(Params<T> P) {
   }
   if (!valid) return;
 
+  if constexpr (kFuse) {   // the state after the last step, once
+    store_kin();
+    if constexpr (kPid) {
+#pragma unroll
+      for (int i = 0; i < 9; ++i) SA.st(QS_F_PID_INT_POS + i, pid[i]);
+    }
+    if constexpr (kHover) {
+      if (any_reset) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) SA.st(QS_F_TARGET + i, tgt[i]);
+      }
+    }
+    return;
+  }
   // ---------------- store state of the envs that (auto-)reset
   if (do_reset) {
     store_kin();

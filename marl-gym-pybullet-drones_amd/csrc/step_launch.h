@@ -6,6 +6,11 @@ namespace qs {
 // Launches step_kernel<T, TASK, act, ...> (control frequency and physics chosen
 // from cf/pf/ph).  Defined and explicitly instantiated in one translation unit
 // per task family.  Returns false for an unknown action type.
-template <class T, int TASK>
-bool launch_task(int act, int grid, size_t lds, hipStream_t st, const Params<T>& P, int cf, int pf, int ph);
+// FUSE = 1: the multi-step instances (ParamsMany: P.nsteps steps per launch,
+// P.io[]), in translation units of their own.  `fn`, if given, receives the kernel's
+// function pointer (what a graph kernel node names); `select_only` looks the
+// kernel up without launching it.
+template <class T, int TASK, int FUSE = 0>
+bool launch_task(int act, int grid, size_t lds, hipStream_t st, const KernelParams<T, FUSE>& P, int cf, int pf, int ph,
+                 const void** fn = nullptr, bool select_only = false);
 }  // namespace qs

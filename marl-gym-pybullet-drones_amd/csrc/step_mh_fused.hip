@@ -1,0 +1,4 @@
+// step_mh_fused.hip — multi-step (FUSE) step-kernel instantiations for QS_TASK_MULTIHOVER.
+#include "step_launch_impl.h"
+
+QS_INSTANTIATE_LAUNCH_FUSED(QS_TASK_MULTIHOVER)

@@ -196,6 +196,14 @@ class QuadSwarm:
                     or actions.numel() != self.num_agents * self.act_dim):
                 raise ValueError(f"actions must be a contiguous float32 ({self.num_envs},{self.num_drones},"
                                  f"{self.act_dim}) tensor on {self.device}")
+        so, res = self._step_out(obs, reward, terminated, truncated, terminal_obs, reasons, actions_out,
+                                 want_terminal, want_reasons)
+        L.check(self.lib.qs_step(self._h, L.ptr(actions), ctypes.byref(so), self._stream()), "qs_step")
+        return res
+
+    def _step_out(self, obs=None, reward=None, terminated=None, truncated=None, terminal_obs=None, reasons=None,
+                  actions_out=None, want_terminal=False, want_reasons=False):
+        """The qs_step_out record and the StepResult of one step's output keywords."""
         obs = self.obs if obs is None else obs
         reward = self.reward if reward is None else reward
         terminated = self.terminated if terminated is None else terminated
@@ -213,8 +221,19 @@ class QuadSwarm:
             reasons = self.reasons
         so = L.QsStepOut(L.ptr(obs), L.ptr(reward), L.ptr(terminated), L.ptr(truncated), L.ptr(terminal_obs),
                          L.ptr(reasons), L.ptr(actions_out))
-        L.check(self.lib.qs_step(self._h, L.ptr(actions), ctypes.byref(so), self._stream()), "qs_step")
-        return StepResult(obs, reward, terminated, truncated, terminal_obs, reasons, actions_out)
+        return so, StepResult(obs, reward, terminated, truncated, terminal_obs, reasons, actions_out)
+
+    def step_many(self, outs):
+        """len(outs) consecutive control steps under the synthetic random policy, as
+        `step(None, **outs[j])` for each j, but several steps to a launch with the
+        envs' state kept on-chip in between (qs_step_many; the depth is
+        QS_MAX_FUSED_STEPS at construction).  outs: one dict of step()'s output
+        keywords per step; steps share a launch only while their buffers are
+        distinct.  Returns the steps' StepResults."""
+        recs = [self._step_out(**kw) for kw in outs]
+        arr = (L.QsStepOut * max(1, len(recs)))(*[so for so, _ in recs])
+        L.check(self.lib.qs_step_many(self._h, len(recs), arr, self._stream()), "qs_step_many")
+        return [res for _, res in recs]
 
     # ------------------------------------------------------------ state I/O
     def _state_buf(self, block):
