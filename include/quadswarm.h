@@ -218,14 +218,23 @@ int qs_reset(qs_handle* h, uint64_t seed, float* obs, void* stream);
 int qs_reset_envs(qs_handle* h, const uint8_t* mask, float* obs, void* stream);
 
 /* One control step of every env: the reference's BaseAviary.step for all
- * envs + the worker's auto-reset.  actions: [E][D][A] float32 or NULL. */
+ * envs + the worker's auto-reset.  actions: [E][D][A] float32 or NULL.
+ *
+ * Environment QS_WAVE_REDUCE (read once, at qs_create; default 1): in the
+ * multi-step launches (qs_step_many, captured qs_step) with 2, 4, 8 or 16
+ * drones per env the per-env reward sum, done flag and reset flag are formed
+ * inside the wavefront (DPP reads, ballots); 0 keeps them on the LDS path that
+ * every other drone count, the MARL tasks and the single-step launches take.
+ * Results are bit-identical either way; the switch is there for A/B runs and
+ * tests. */
 int qs_step(qs_handle* h, const float* actions, const qs_step_out* out,
             void* stream);
 
 /* n consecutive control steps under the random policy (qs_step with actions
  * = NULL, n times); step j writes outs[j].  The steps run K to a launch, K =
  * the handle's fusion depth (environment QS_MAX_FUSED_STEPS at qs_create,
- * 1..16), with the envs' state kept on-chip between the steps of a launch;
+ * 1..32: the depth cap, one set of output pointers per step in the kernel's
+ * arguments), with the envs' state kept on-chip between the steps of a launch;
  * every output is bit-identical to n qs_step calls.  Steps share a launch only
  * while no output range of one overlaps an output range of another, and
  * handles that run the deferred reset search after each step (MultiHover

@@ -16,6 +16,7 @@
 #include "quadswarm.h"
 #include "step_launch.h"
 #include "step_fuse.h"
+#include "step_trunc.h"
 
 static_assert(qs::kFuseMax == qs::kMaxFuse, "step_fuse.h and step_kernel.h disagree on the fusion depth");
 
@@ -162,6 +163,10 @@ struct qs_handle {
   // stream capture that the last qs_step made and the next one may grow
   // (step_fuse.h), with the launch parameters the node holds.
   int fuse_depth = 1;
+  // Multi-step launches: per-env reward / done / reset flags inside the wave (DPP,
+  // ballots) where an env is 2, 4, 8 or 16 lanes; QS_WAVE_REDUCE=0 keeps them on the
+  // LDS path (the A/B switch)
+  bool wave_reduce = true;
   qs::FuseGroup fuse;
   qs::ParamsMany<float> fuse_pf;
   qs::ParamsMany<double> fuse_pd;
@@ -197,6 +202,8 @@ template <class T> static void fill_params(const qs_handle* h, qs::Params<T>& P)
   P.EPB = envs_per_wave(h);
   P.aux = s.aux_forces; P.flags = s.flags; P.pyb_freq = s.pyb_freq; P.task = s.task;
   P.ep_len_sec = s.episode_len_sec;
+  P.trunc_at = qs::trunc_threshold(s.pyb_freq, s.episode_len_sec);
+  P.wave_reduce = h->wave_reduce ? 1 : 0;
   P.k0 = (uint32_t)h->seed; P.k1 = (uint32_t)(h->seed >> 32);
   P.env_offset = s.env_offset;
   P.reset_queue = h->rq;
@@ -462,8 +469,8 @@ const char* qs_last_error(void) { return g_err.c_str(); }
 int qs_abi_version(void) { return QS_ABI_VERSION; }
 
 // Default fusion depth of the synthetic-policy rollout (QS_MAX_FUSED_STEPS
-// overrides it): the fastest of 4 / 8 / 16 on the C3 bench (profiles/step_fusion_ab.json).
-static constexpr int kDefaultFusedSteps = 16;
+// overrides it): the fastest of 1 / 8 / 16 / 24 / 32 on the C3 bench (profiles/step_trim_ab.json).
+static constexpr int kDefaultFusedSteps = 32;
 
 int qs_create(const qs_spec* spec, int device, qs_handle** out) {
   if (!spec || !out) return fail(QS_E_INVALID, "qs_create: null argument");
@@ -513,6 +520,7 @@ int qs_create(const qs_spec* spec, int device, qs_handle** out) {
     const long k = std::strtol(v, &end, 10);
     if (end != v) h->fuse_depth = (int)std::min<long>(std::max<long>(k, 1), qs::kMaxFuse);
   }
+  if (const char* v = getenv("QS_WAVE_REDUCE")) h->wave_reduce = std::strtol(v, nullptr, 10) != 0;   // read once, here
   h->spec = s;
   h->spec.initial_xyzs = nullptr;
   h->device = device;

@@ -15,7 +15,7 @@
 
 namespace qs {
 
-constexpr int kFuseMax = 16;    // = kMaxFuse (step_kernel.h), checked in quadswarm.hip
+constexpr int kFuseMax = 32;    // = kMaxFuse (step_kernel.h), checked in quadswarm.hip
 constexpr int kFuseOuts = 7;    // obs, reward, terminated, truncated, terminal_obs, reasons, actions_out
 
 struct FuseOuts {

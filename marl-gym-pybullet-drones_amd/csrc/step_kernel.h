@@ -228,14 +228,10 @@ __device__ __forceinline__ U4 philox(U4 c, uint32_t k0, uint32_t k1) {
   for (int r = 0; r < 10; ++r) {
     if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
     // one 32x32->64 product per multiplier (a single v_mad_u64_u32, where separate
-    // lo/hi halves are two quarter-rate v_mul_lo/v_mul_hi)
-#ifndef QS_PHILOX_MAD64
-    uint32_t lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
-    uint32_t lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
-#else
+    // lo/hi halves are two quarter-rate v_mul_lo/v_mul_hi: the multi-step C3 step
+    // measured 3.75 against 3.82 µs, profiles/step_trim_items.json)
     const uint64_t p0 = (uint64_t)0xD2511F53u * c.x, p1 = (uint64_t)0xCD9E8D57u * c.z;
     const uint32_t lo0 = (uint32_t)p0, hi0 = (uint32_t)(p0 >> 32), lo1 = (uint32_t)p1, hi1 = (uint32_t)(p1 >> 32);
-#endif
     c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
   }
   return c;
@@ -246,7 +242,7 @@ template <class T> __device__ __forceinline__ T u01(uint32_t x) { return T(x >> 
 // -------------------------------------------------------------- parameters
 // Outputs of one control step (all optional).  A multi-step launch (step_kernel
 // FUSE) writes step j of the launch through ParamsMany::io[j].
-constexpr int kMaxFuse = 16;
+constexpr int kMaxFuse = 32;
 template <class T> struct StepIO {
   float* obs;
   T* rew;
@@ -265,6 +261,8 @@ template <class T> struct Params {
   uint32_t aux, flags;
   int pyb_freq;
   double ep_len_sec;
+  int trunc_at;           // smallest step_counter with step_counter / pyb_freq > ep_len_sec (step_trunc.h)
+  int wave_reduce;        // multi-step instances: per-env reward / done / reset flags through DPP and ballots (QS_WAVE_REDUCE)
   uint32_t k0, k1;
   long long env_offset;
   T dt, hdt, hdt2, ctrl_dt, ctrl_hz;   // PYB_TIMESTEP, dt/2, (dt/2)², CTRL_TIMESTEP, CTRL_FREQ
@@ -702,6 +700,32 @@ __device__ __forceinline__ float dw_term(float dz, float d2) {
 template <int K> __device__ __forceinline__ float row_ror(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + K, 0xF, 0xF, false));
 }
+// DPP row_shl:K — a lane reads lane i + K of its 16-lane row (lanes whose source
+// falls outside the row read 0).  Doubles move as two dwords.
+template <int K> __device__ __forceinline__ int row_shl(int v) {
+  return __builtin_amdgcn_update_dpp(0, v, 0x100 + K, 0xF, 0xF, true);
+}
+template <int K> __device__ __forceinline__ float row_shl(float v) {
+  return __builtin_bit_cast(float, row_shl<K>(__builtin_bit_cast(int, v)));
+}
+template <int K> __device__ __forceinline__ double row_shl(double v) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+  const unsigned lo = (unsigned)row_shl<K>((int)(unsigned)u), hi = (unsigned)row_shl<K>((int)(unsigned)(u >> 32));
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+// Per-env reward sum and reason OR for D ∈ {2, 4, 8, 16} (an env is D adjacent
+// lanes of one DPP row): the env's first lane adds its neighbours' terms in drone
+// order, ((0 + r0) + r1) + …, the order of the LDS loop it stands in for.  Every
+// lane of the wave executes it (a DPP read of an inactive lane returns nothing);
+// only the first lane of an env holds the env's values afterwards.
+template <int DD, int K = 1, class T> __device__ __forceinline__ void env_reduce(T r, int b, T& rsum, int& any) {
+  if constexpr (K == 1) { rsum = T(0) + r; any = b; }
+  if constexpr (K < DD) {
+    rsum += row_shl<K>(r);
+    any |= row_shl<K>(b);
+    env_reduce<DD, K + 1>(r, b, rsum, any);
+  }
+}
 // D = 16: an env is one DPP row.  The pair term depends on |Δz| and Δxy² only,
 // so each unordered pair is formed once: for K = 1..7 a lane forms the pair with
 // its row neighbour K away, keeps the term when that drone is above it and hands
@@ -755,13 +779,17 @@ template <class T> __device__ __forceinline__ int launch_steps(const ParamsMany<
 // same for DroneModel.CF2P (QS_FLAG_CF2P).
 // FUSE = 1: P.nsteps consecutive synthetic-policy control steps (MODE_STEP, no
 // trainer actions, no deferred reset queue) of the same envs in one launch.  The
-// loads run once, then every step does the single step's operations in the
-// single step's order on values that stay in registers (state, PID integrators,
-// target, env counters, the action-history ring); step j's outputs go to
-// P.io[j] (ParamsMany), the new action to its global ring slot (store only) and
-// into the register / LDS ring, and the state is stored once after the last
-// step.  Bit-identical to P.nsteps launches of the FUSE = 0 instance, which
-// compiles to the code it had before the flag existed (no loop is emitted for it).
+// loads run once, then every step forms the single step's values by the single
+// step's operations on values that stay in registers (state, PID integrators,
+// target, env counters, the action history); step j's outputs go to P.io[j]
+// (ParamsMany), the new action to its global ring slot (store only) and into the
+// registers / the LDS ring, and the state is stored once after the last step.
+// What only the launch boundary made necessary is done once per launch or not
+// at all: the PID's attitude is the previous step's readback, the register
+// history is held in age order (fixed obs columns, a shift per step), and the
+// per-env reduction and flags stay inside the wave.
+// Bit-identical to P.nsteps launches of the FUSE = 0 instance (no loop is
+// emitted for that one).
 template <class T, int TASK, int ACT, int CF, int PHYS, int AUXM, int FUSE = 0>
 __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   using F = M<T>;
@@ -785,6 +813,13 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   const bool valid = (lenv < P.EPB) && (e < P.E);
   const int a = e * D + d;
   const uint32_t genv = (uint32_t)(P.env_offset + e);
+  // kBlock == 64 is one wave: an env of 2, 4, 8 or 16 drones lies inside one
+  // 16-lane DPP row, and the per-env reduction and flags need no LDS.  Multi-step
+  // instances only: with the run-time choice between the two paths in it, the
+  // single step (bound by its loads and stores, its waits counted exactly by the
+  // compiler) ran 9.00 µs against 8.84 (C3; 8.91 as it is)
+  static_assert(kBlock == 64, "the wave reduction assumes one wave per workgroup");
+  const bool wave_red = kFuse && !kMarl && P.wave_reduce != 0 && (D == 2 || D == 4 || D == 8 || D == 16);
   SoA<T> SA;
   SA.rsrc = __builtin_amdgcn_make_buffer_rsrc(P.st, 0, (int)((unsigned)QS_AGENT_FIELDS * (unsigned)N * sizeof(T)), 0x00020000);
   SA.fstride = (unsigned)N * (unsigned)sizeof(T);
@@ -935,6 +970,34 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   // FUSE: every load has landed before the loop, which issues none (its stores
   // are never waited for: nothing reads what they write).
   if constexpr (kFuse) wait_vm0();
+  // FUSE, register ring: the H − 1 older entries go into age order once, oldest
+  // first in hreg[0 .. H−2] (a per-lane rotation by the ring head, as
+  // conditional rotations by 1, 2, 4, … slots: H·A selects each).  The loop then
+  // writes its obs columns from fixed registers and ages the history by a shift.
+  constexpr bool kAged = kFuse && CF != 0;
+  if constexpr (kAged) {
+    const int rot = wslot + 1 == HR ? 0 : wslot + 1;   // slot of the oldest older entry
+#pragma unroll
+    for (int b = 1; b < HR; b <<= 1) {
+      const bool on = (rot & b) != 0;
+      float t[HR][A];
+#pragma unroll
+      for (int sl = 0; sl < HR; ++sl)
+#pragma unroll
+        for (int k = 0; k < A; ++k) t[sl][k] = hreg[(sl + b) % HR][k];
+#pragma unroll
+      for (int sl = 0; sl < HR; ++sl)
+#pragma unroll
+        for (int k = 0; k < A; ++k) hreg[sl][k] = on ? t[sl][k] : hreg[sl][k];
+    }
+  }
+  // FUSE with a PID: the attitude each step's PID consumes (DSLPIDControl.py:240)
+  // is the previous step's readback of the same quaternion; only the first step
+  // of the launch has none
+  constexpr bool kCarryRpy = kFuse && kPid;
+  if constexpr (kCarryRpy) {
+    if (valid && !qs_dev::kNoCompute) quat_to_rpy(q, rpy);
+  }
   // (a do-while whose condition is the constant false without FUSE: no loop
   // is emitted for the single-step instances)
   int ks = 0;
@@ -974,7 +1037,8 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
         T r = T(cf2x::HOVER_RPM) * (T(1) + T(0.05) * T(act[0]));
         rpm[0] = rpm[1] = rpm[2] = rpm[3] = r;
       } else {
-        if (!qs_dev::kNoCompute) quat_to_rpy(q, rpy);   // DSLPIDControl.py:240 (and the VEL target yaw, BRL:221)
+        // DSLPIDControl.py:240 (and the VEL target yaw, BRL:221); FUSE: carried from the readback
+        if (!qs_dev::kNoCompute && !kCarryRpy) quat_to_rpy(q, rpy);
         if constexpr (ACT == QS_ACT_ONE_D_PID) {
           T tp[3] = {pos[0], pos[1], pos[2] + T(0.1) * T(act[0])};
           dsl_pid<T, kP>(P.ctrl_dt, P.ctrl_hz, pid, pos, q, vel, rpy, tp, T(0), z3, rpm);
@@ -1463,24 +1527,35 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
         if (pos[2] < T(0.05) || pos[2] > T(3.0)) bits |= QS_REASON_ZRANGE;
       }
     }
-    s.rew[tid] = rterm;
-    s.bits[tid] = bits;
-    if constexpr (kMarl) {
+    // per-env reduction in drone order (reference: reward += ... for i in range(D)):
+    // inside the wave when an env is 2, 4, 8 or 16 lanes of a DPP row, through
+    // LDS otherwise (and for the MARL tasks, which read positions there anyway)
+    T rsum = 0;
+    int any = 0;
+    if (wave_red) {   // wave-uniform
+      if (D == 8) env_reduce<8>(rterm, (int)bits, rsum, any);
+      else if (D == 16) env_reduce<16>(rterm, (int)bits, rsum, any);
+      else if (D == 4) env_reduce<4>(rterm, (int)bits, rsum, any);
+      else env_reduce<2>(rterm, (int)bits, rsum, any);
+    } else {
+      s.rew[tid] = rterm;
+      s.bits[tid] = bits;
+      if constexpr (kMarl) {
 #pragma unroll
-      for (int i = 0; i < 3; ++i) { s.cand[tid][i] = pos[i]; s.velw[tid][i] = vel[i]; }
+        for (int i = 0; i < 3; ++i) { s.cand[tid][i] = pos[i]; s.velw[tid][i] = vel[i]; }
+      }
+      __syncthreads();
+      if (valid && d == 0) {
+        for (int j = 0; j < D; ++j) { rsum += s.rew[tid + j]; any |= s.bits[tid + j]; }
+      }
     }
-    __syncthreads();
-    // per-env reduction in drone order (reference: reward += ... for i in range(D))
     bool dn = false;
     double ret = 0;
     int len = 0;
     if (valid && d == 0) {
-      T rsum = 0;
-      uint8_t any = 0;
-      for (int j = 0; j < D; ++j) { rsum += s.rew[tid + j]; any |= s.bits[tid + j]; }
       T r = rsum / T(D);
       bool te = any != 0;
-      bool tr = ((double)step_counter / (double)P.pyb_freq) > P.ep_len_sec;   // MultiHoverAviary.py:267-268
+      bool tr = step_counter >= P.trunc_at;   // step_counter / PYB_FREQ > EPISODE_LEN_SEC (MultiHoverAviary.py:267-268, step_trunc.h)
       if constexpr (kMarl) {
         r = marl_reward<T>(P.task, &s.cand[tid], &s.velw[tid], D);
         te = P.task == QS_TASK_MEETUP && meetup_met<T>(&s.cand[tid], D);
@@ -1494,7 +1569,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
       dn = te || tr;
       ep_ret_out = dn ? 0.0 : ret;
       ep_len_out = dn ? 0 : len;
-      s.done[lenv] = dn;
+      if (!wave_red) s.done[lenv] = dn;
     }
     // Episode log (VecRecordEpisodeStatistics, record_episode_statistics.py:155-166):
     // each env appends to its own ring, slot = its logged count mod log_per_env —
@@ -1508,8 +1583,12 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     }
     if (io.reasons && valid) io.reasons[a] = kMarl ? 0 : bits;
     step_counter += S;   // BaseAviary.py:382
-    __syncthreads();
-    done_env = valid && s.done[lenv];
+    if (wave_red) {   // the env's first lane holds dn: its bit of the wave's ballot
+      done_env = valid && ((__ballot(dn) >> (tid - d)) & 1ull) != 0;
+    } else {
+      __syncthreads();
+      done_env = valid && s.done[lenv];
+    }
   } else if (mode == MODE_RESET_ALL) {
     wait_vm0();
     // qs_reset: every env starts episode 0 (history is zero after qs_reset)
@@ -1545,7 +1624,12 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     // history, oldest first: ring slots base .. base+H-2 (mod H), then this
     // step's action (BaseRLAviary.py:317-318)
     const int base = mode == MODE_STEP ? wslot + 1 : wslot;
-    if constexpr (CF != 0) {   // register ring: slot sl goes to column (sl - base) mod H
+    if constexpr (kAged) {   // registers in age order: fixed columns
+#pragma unroll
+      for (int col = 0; col < HR - 1; ++col)
+#pragma unroll
+        for (int k = 0; k < A; ++k) o[12 + col * A + k] = hreg[col][k];
+    } else if constexpr (CF != 0) {   // register ring: slot sl goes to column (sl - base) mod H
 #pragma unroll
       for (int sl = 0; sl < HR; ++sl) {
         int col = sl - base;
@@ -1583,11 +1667,17 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   if (valid && done_env && mode == MODE_STEP && io.tobs) write_obs_row(io.tobs + (size_t)a * O, obs_sc);
 
   // ---------------- auto-reset (worker.step_env → env.reset)
-  s.any = 0;
-  __syncthreads();
-  if (do_reset && d == 0) s.any = 1;
-  __syncthreads();
-  if (s.any) {
+  bool some_reset;   // workgroup-uniform: some env of this wave resets
+  if (wave_red) {
+    some_reset = __ballot(do_reset) != 0;
+  } else {
+    s.any = 0;
+    __syncthreads();
+    if (do_reset && d == 0) s.any = 1;
+    __syncthreads();
+    some_reset = s.any != 0;
+  }
+  if (some_reset) {
     if (d == 0 && lenv < P.EPB) s.need[lenv] = do_reset ? 1 : 0;
     if (mode != MODE_RESET_ALL && do_reset) episode += 1;
     T init[3] = {orig[0], orig[1], orig[2]};
@@ -1724,10 +1814,24 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     }
   }
   QS_STAMP(6);
+  if constexpr (kCarryRpy) {
+    // An env that reset showed +0 angles in its obs; what its next PID call reads
+    // is the readback of the reset quaternion (pitch = asin(−0) = −0), through
+    // the same function (constant operands: it folds)
+    if (do_reset) {
+      const T q0[4] = {0, 0, 0, 1};
+      quat_to_rpy(q0, rpy);
+    }
+  }
   if constexpr (kFuse) {
     // the next step's view of the ring: this step's action takes slot wslot
     // (the launches' `total % H`; total advances by one per step)
-    if constexpr (CF != 0) {
+    if constexpr (kAged) {   // every entry ages by one step; this step's action is the newest older entry
+#pragma unroll
+      for (int col = 0; col < HR - 1; ++col)
+#pragma unroll
+        for (int k = 0; k < A; ++k) hreg[col][k] = col == HR - 2 ? cur_act[k] : hreg[col + 1][k];
+    } else if constexpr (CF != 0) {
 #pragma unroll
       for (int sl = 0; sl < HR; ++sl)
 #pragma unroll
