@@ -19,6 +19,8 @@
 #include "step_trunc.h"
 
 static_assert(qs::kFuseMax == qs::kMaxFuse, "step_fuse.h and step_kernel.h disagree on the fusion depth");
+static_assert(qs::kObsPipeMaxRow == qs::kObsPipeMaxO && qs::kObsPipeRows == qs::kBlock,
+              "step_fuse.h and step_kernel.h disagree on the fast obs path's shape");
 
 namespace qs {
 // Calibration kernel: dword per lane, grid-stride (MI355X_MICROARCH §HBM).
@@ -257,6 +259,15 @@ static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t
   if (lds_plan(h->dims, P.EPB, (grid + h->num_cu - 1) / h->num_cu, &P.stage_rows, &lds) != QS_OK)
     return fail(QS_E_INVALID, "launch: action history does not fit in LDS (ctrl_freq too high)");
   const qs_spec& s = h->spec;
+  if constexpr (FUSE != 0) {
+    // the fast obs path, decided per launch (step_fuse.h); the instances with the
+    // compile-time control frequency are the ones launch_one picks under `fixed_cf`
+    const bool fixed_cf = !(s.flags & QS_FLAG_CF2P) && s.pyb_freq == 240 &&
+                          s.ctrl_freq == (s.task == QS_TASK_SPIRAL ? 48 : 30);
+    const void* obs[qs::kMaxFuse];
+    for (int j = 0; j < P.nsteps; ++j) obs[j] = P.io[j].obs;
+    P.obs_pipe = qs::obs_pipe_ok(fixed_cf, P.stage_rows, P.EPB * P.D, P.O, obs, P.nsteps) ? 1 : 0;
+  }
   const void* fn = nullptr;
   bool ok;
   if (s.task == QS_TASK_MULTIHOVER)

@@ -22,6 +22,29 @@ struct FuseOuts {
   const void* p[kFuseOuts];
 };
 
+// May a multi-step launch take the kernel's fast obs path (ParamsMany::obs_pipe)?
+// There a workgroup's obs rows of a step wait in LDS and leave as whole float4
+// pieces of one contiguous span during the next step, so:
+//  - the kernel instance is one with the compile-time control frequency
+//    (`fixed_cf`; the others do not carry the path),
+//  - a row is at most kObsPipeMaxRow floats (a lane holds ⌈row/4⌉ float4 in flight),
+//  - a workgroup holds kObsPipeRows `rows` (= envs per workgroup × drones: every
+//    lane of the wave a drone), so the pieces' offsets are constants and the
+//    span, rows × row_floats floats, is a whole number of float4 that starts a
+//    multiple of 16 bytes from the buffer's start in every workgroup,
+//  - all of them are staged in one pass,
+//  - every obs buffer of the launch is 16-byte aligned (a step may have none).
+// Any other launch takes the general path.
+constexpr int kObsPipeMaxRow = 32;   // = kObsPipeMaxO (step_kernel.h), checked in quadswarm.hip
+constexpr int kObsPipeRows = 64;     // = kBlock (step_kernel.h), checked in quadswarm.hip
+inline bool obs_pipe_ok(bool fixed_cf, int stage_rows, int rows, int row_floats, const void* const* obs, int nsteps) {
+  if (!fixed_cf || rows != kObsPipeRows || row_floats <= 0 || row_floats > kObsPipeMaxRow) return false;
+  if (stage_rows < rows) return false;
+  for (int j = 0; j < nsteps; ++j)
+    if (obs[j] && ((uintptr_t)obs[j] & 15u) != 0) return false;
+  return true;
+}
+
 struct FuseGroup {
   bool live = false;
   unsigned long long capture_id = 0;   // the stream capture the node belongs to

@@ -297,6 +297,11 @@ template <class T> struct Params {
 // it they compiled to different code).
 template <class T> struct ParamsMany : Params<T> {
   int nsteps;
+  // The launch's obs spans take the fast path (step_fuse.h, obs_pipe_ok): a full
+  // wave of rows staged in one pass, every buffer 16-byte aligned.  A step then
+  // leaves its rows in LDS and the next step of the launch copies them out under
+  // its own PID (the last step's are copied after the loop).
+  int obs_pipe;
   StepIO<T> io[kMaxFuse];
 };
 template <class T, int FUSE> using KernelParams = std::conditional_t<FUSE != 0, ParamsMany<T>, Params<T>>;
@@ -553,6 +558,12 @@ __device__ void eval_candidate(const Params<T>& P, Shared<T>& s, const T orig[3]
 #ifndef QS_NT_OBS
 #define QS_NT_OBS 1
 #endif
+// Multi-step instances: the obs span copied out under the next step's PID
+// (DESIGN.md §4a); a dev build switches it off to measure it.
+#ifndef QS_OBS_PIPE
+#define QS_OBS_PIPE 1
+#endif
+constexpr int kObsPipeMaxO = 32;   // = qs::kObsPipeMaxRow (step_fuse.h), checked in quadswarm.hip
 typedef float f4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void obs_store4(float4* p, float4 v) {
   if constexpr (QS_NT_OBS) __builtin_nontemporal_store(f4v{v.x, v.y, v.z, v.w}, reinterpret_cast<f4v*>(p));
@@ -762,6 +773,8 @@ __device__ __forceinline__ float downwash16(float px, float py, float pz) {
 
 template <class T> __device__ __forceinline__ int launch_steps(const Params<T>&) { return 1; }
 template <class T> __device__ __forceinline__ int launch_steps(const ParamsMany<T>& P) { return P.nsteps; }
+template <class T> __device__ __forceinline__ bool launch_obs_pipe(const Params<T>&) { return false; }
+template <class T> __device__ __forceinline__ bool launch_obs_pipe(const ParamsMany<T>& P) { return P.obs_pipe != 0; }
 
 // ---------------------------------------------------------------- the step
 // TASK (qs_task) and ACT (qs_action_type) are compile-time: each launch runs
@@ -998,6 +1011,37 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   if constexpr (kCarryRpy) {
     if (valid && !qs_dev::kNoCompute) quat_to_rpy(q, rpy);
   }
+  // FUSE, obs fast path (ParamsMany::obs_pipe; a workgroup with all its EPB envs,
+  // EPB · D = 64 rows): a step leaves its rows in the stage and `pend`, the start
+  // of its span in HBM; the next step reads the span back at its top (all reads
+  // issued at once, a float4 per lane each, constant offsets), runs its action
+  // draw and PID over their latency and stores them.  One stage is enough: the
+  // LDS runs a wave's operations in issue order, so the rows the next step writes
+  // cannot overtake these reads (kBlock == 64: the wave is the workgroup).  The
+  // last step's span is copied after the loop.  Instances whose row is wider than
+  // kObsPipeMaxO floats keep the general path (the reads in flight are ⌈O/4⌉
+  // float4 registers per lane).
+  constexpr int kO = CF ? 12 + (CF / 2) * A + (kSpiral ? 11 : 0) : 0;
+  constexpr bool kPipe = kFuse && QS_OBS_PIPE && CF != 0 && kO <= kObsPipeMaxO;
+  constexpr int kSpan4 = kPipe ? kO * (kBlock / 4) : 1;        // float4 pieces of a 64-row span
+  constexpr int kPipeIt = (kSpan4 + kBlock - 1) / kBlock;       // pieces per lane
+  constexpr int kPipeTail = kSpan4 - (kPipeIt - 1) * kBlock;    // lanes of the last piece
+  bool pipe = false;             // workgroup-uniform
+  float* pend = nullptr;         // workgroup-uniform: the span the stage is waiting to go to
+  if constexpr (kPipe) pipe = launch_obs_pipe(P) && P.EPB * D == kBlock && (int)blockIdx.x * P.EPB + P.EPB <= P.E;
+  auto pend_read = [&](float4 (&v)[kPipeIt]) {
+    const float4* const s4 = reinterpret_cast<const float4*>(stage);
+#pragma unroll
+    for (int i = 0; i < kPipeIt - 1; ++i) v[i] = s4[tid + kBlock * i];
+    // (lanes past the end re-read the last piece and store nothing)
+    v[kPipeIt - 1] = s4[min(tid, kPipeTail - 1) + kBlock * (kPipeIt - 1)];
+  };
+  auto pend_store = [&](const float4 (&v)[kPipeIt], float* g) {
+    float4* const g4 = reinterpret_cast<float4*>(g);
+#pragma unroll
+    for (int i = 0; i < kPipeIt - 1; ++i) obs_store4(g4 + tid + kBlock * i, v[i]);
+    if (tid < kPipeTail) obs_store4(g4 + tid + kBlock * (kPipeIt - 1), v[kPipeIt - 1]);
+  };
   // (a do-while whose condition is the constant false without FUSE: no loop
   // is emitted for the single-step instances)
   int ks = 0;
@@ -1024,6 +1068,13 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     }
   }
   QS_STAMP(1);
+  // the previous step's obs span: every read issued here, stored after the PID
+  float4 pv[kPipeIt];
+  const bool pend_now = kPipe && pend != nullptr;   // workgroup-uniform
+  if constexpr (kPipe) {
+    if (pend_now) pend_read(pv);
+    issue_fence();
+  }
   if (mode == MODE_STEP) {
     const float* act = cur_act;
     // ---------------- _preprocessAction (BaseRLAviary.py:188-239)
@@ -1065,6 +1116,12 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     // let the action draw and the PID start as soon as the state loads land,
     // with the history LDS-DMA (issued last) still streaming.
     if constexpr (!kFuse) wait_vm0();
+    if constexpr (kPipe) {   // the reads have had the PID to land: one wait, then the stores
+      if (pend_now) {
+        issue_fence();
+        pend_store(pv, pend);
+      }
+    }
     if (valid) {
       // one vector store per lane for the A components (a wave writes whole
       // lines; per-component dword stores left 16-B-strided partial lines)
@@ -1182,6 +1239,12 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
       constexpr float kHdt = float(kDt / 2), kHdt2 = float(kDt / 2 * (kDt / 2));
       const float dtm = float(kDt / cf2x::M);
       // exp-map coefficients: c = cos θ, k = sin θ / |ω|, θ = |ω| dt / 2
+      // (both branches below stay exec-mask branches in every instance: the
+      // multi-step instances with the series evaluated by all lanes and the
+      // sin/cos block behind one wave-uniform test measured no faster, and with
+      // the quaternion update kept by select as well the substeps became one
+      // block whose velocity update the compiler contracted differently, 1 ulp
+      // off the single step — DESIGN.md §9j)
       auto expmap = [&](float wn2, float& c, float& k) {
         const float u = wn2 * kHdt2;
         if (u < 0.0625f) {
@@ -1781,8 +1844,15 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
 
   QS_STAMP(5);
   // ---------------- obs output
+  if constexpr (kPipe) pend = nullptr;   // (the span of the step before went out above)
   if (io.obs) {
-    if (mode == MODE_RESET_MASK) {
+    if (kPipe && pipe) {
+      // fast path: the rows stay in the stage; the next step (or the code after
+      // the loop) copies the span out
+      if (valid) write_obs_row(stage + tid * O, obs_sc);
+      issue_fence();
+      pend = io.obs + (size_t)blockIdx.x * P.EPB * D * O;
+    } else if (mode == MODE_RESET_MASK) {
       if (valid && do_reset) write_obs_row(io.obs + (size_t)a * O, obs_sc);
     } else {
       // The block's obs rows are one contiguous span of HBM: build them in LDS
@@ -1846,6 +1916,13 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     wslot = wslot + 1 == H ? 0 : wslot + 1;
   }
   } while (kFuse && ++ks < launch_steps(P));   // control steps of this launch
+  if constexpr (kPipe) {   // the last step's obs span
+    if (pend != nullptr) {
+      float4 pv[kPipeIt];
+      pend_read(pv);
+      pend_store(pv, pend);
+    }
+  }
   // ---------------- per-env records: staged in LDS, stored as one span
   if (valid && d == 0) {
     int32_t* r = &s.rec[lenv * kEnvRec];

@@ -51,7 +51,8 @@ d = np.diff(st[:, :7], axis=1)
 print("per-wave phase durations median:", np.round(np.median(d, axis=0), 2))
 if MANY:
     # the last iteration: draw (loop top -> 1) is not stamped; 1->2 PID + action stores, 2->3 substeps + readback,
-    # 3->4 reward / reduction / log, 4->5 terminal obs + auto-reset, 5->6 obs span
+    # 3->4 reward / reduction / log, 4->5 terminal obs + auto-reset, 5->6 obs span (on the fast obs path: the rows
+    # into LDS only; the span's read-back brackets the draw and its stores fall into 1->2 of the next iteration)
     it = st[:, 6] - st[:, 1]
     per = (st[:, 6] - st[:, 0]) / MANY
     print("last iteration, per-wave medians (us): " + "  ".join(
