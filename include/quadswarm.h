@@ -50,7 +50,8 @@ extern "C" {
 #endif
 
 #define QS_ABI_VERSION 4   /* 2: qs_episode_log reports the records it wrote; 3: qs_ppo_small_layout takes
-                              the caller's entry count; 4: QS_FLAG_CF2P */
+                              the caller's entry count; 4: QS_FLAG_CF2P (qs_step_seq came later as a new
+                              symbol: nothing that existed changed, so the number stayed) */
 
 /* ---- status codes ------------------------------------------------------ */
 #define QS_OK 0
@@ -247,6 +248,34 @@ int qs_step(qs_handle* h, const float* actions, const qs_step_out* out,
  * recorded on the capturing stream between two such steps and waited for by
  * another stream therefore marks the whole node, later steps included. */
 int qs_step_many(qs_handle* h, int n, const qs_step_out* outs, void* stream);
+
+/* n consecutive control steps; step j consumes actions[j] ([E][D][A] float32,
+ * device) and writes outs[j].  Equal, bit for bit, to n qs_step(h, actions[j],
+ * &outs[j], stream) calls.  actions == NULL: exactly qs_step_many.
+ *
+ * `actions` is a host array of n device pointers, read during the call; the
+ * buffers need 4-byte alignment only.  Either every step reads its actions or
+ * none does: an array with a NULL among its entries is QS_E_INVALID.  n < 0, or
+ * n > 0 without outs, is QS_E_INVALID; a call before qs_reset is QS_E_STATE;
+ * n == 0 does nothing.
+ *
+ * Like qs_step_many it runs up to QS_MAX_FUSED_STEPS steps to a launch with the
+ * state on-chip in between.  A launch reads the action rows of all its steps
+ * into LDS before its first step runs, 256 · A bytes per step and workgroup, so
+ * its depth is capped further where that would keep the launch's workgroups
+ * from being resident at once (MultiHover, 16 384 envs × 8 drones, A = 1: 19).
+ * Steps share a launch while
+ *  - their outputs are disjoint across steps (as in qs_step_many),
+ *  - a step's actions overlap no output of an earlier step of the launch, and
+ *  - a step's outputs overlap no actions of an earlier step of the launch;
+ * the launch is cut before a step that breaks one of these, which restores the
+ * order of single steps: feeding step j's actions_out (or obs) to step j + 1
+ * works, one step per launch.  Steps may read the same actions.  Handles that
+ * run the deferred reset search after each step take one step per launch, and
+ * so do the Flock / Meetup / LeaderFollower tasks (their multi-step kernels
+ * round the env reward 1 ulp apart from the single step's). */
+int qs_step_seq(qs_handle* h, int n, const float* const* actions,
+                const qs_step_out* outs, void* stream);
 
 /* Copy a state block between the handle and `buf` (device pointer).
  * dir = 0: handle → buf (get), dir = 1: buf → handle (set). */

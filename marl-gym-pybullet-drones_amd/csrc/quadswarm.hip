@@ -1,8 +1,9 @@
 // quadswarm.hip — host side of the MI355X quadrotor-swarm step: the C-ABI of
 // include/quadswarm.h (handle, state buffers, launches).  The device code is
 // csrc/step_kernel.h; the kernels are instantiated per task family in
-// step_mh.hip / step_spiral.hip / step_marl.hip (single step) and their
-// *_fused.hip twins (several control steps per launch).
+// step_mh.hip / step_spiral.hip / step_marl.hip (single step), their
+// *_fused.hip twins (several control steps per launch) and step_mh_seq.hip /
+// step_spiral_seq.hip (the same over caller-supplied actions).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -21,6 +22,7 @@
 static_assert(qs::kFuseMax == qs::kMaxFuse, "step_fuse.h and step_kernel.h disagree on the fusion depth");
 static_assert(qs::kObsPipeMaxRow == qs::kObsPipeMaxO && qs::kObsPipeRows == qs::kBlock,
               "step_fuse.h and step_kernel.h disagree on the fast obs path's shape");
+static_assert(qs::kSeqStepBytes == qs::kBlock * (int)sizeof(float), "step_fuse.h and step_kernel.h disagree on an action row's LDS");
 
 namespace qs {
 // Calibration kernel: dword per lane, grid-stride (MI355X_MICROARCH §HBM).
@@ -242,6 +244,19 @@ static int lds_plan(const qs_dims& d, int epb, int resident, int* stage_rows, si
   return QS_OK;
 }
 
+// The instances with the compile-time control frequency (launch_one's `cf`, and
+// not DroneModel.CF2P): they keep the action history in registers.
+static bool fixed_ctrl_freq(const qs_spec& s) {
+  return !(s.flags & QS_FLAG_CF2P) && s.pyb_freq == 240 && s.ctrl_freq == (s.task == QS_TASK_SPIRAL ? 48 : 30);
+}
+// Dynamic LDS of a FUSE = 2 launch, without its action rows: lds_plan's bytes,
+// less the history image where the instance does not use it (step_kernel.h puts
+// the action rows first, then the image if any, then the obs stage).
+static size_t seq_lds_base(const qs_handle* h, size_t plan_bytes) {
+  const size_t hist = (size_t)h->dims.hist_len * qs::kBlock * h->dims.act_dim * sizeof(float);
+  return fixed_ctrl_freq(h->spec) ? plan_bytes - hist : plan_bytes;
+}
+
 // What a launch ran (or, select_only, would run): a graph kernel node's fields.
 struct LaunchInfo {
   const void* fn = nullptr;
@@ -251,7 +266,9 @@ struct LaunchInfo {
 
 // Grid, LDS plan (P.stage_rows) and the kernel of a launch; FUSE = 1: the
 // multi-step instance over P.io[0 .. P.nsteps-1] (MODE_STEP, no trainer actions,
-// no deferred reset queue: the callers see to that).  select_only: no launch.
+// no deferred reset queue: the callers see to that); FUSE = 2: the same over the
+// actions P.act[0 .. P.nsteps-1], whose rows take LDS of their own (the caller
+// has capped P.nsteps by seq_depth).  select_only: no launch.
 template <class T, int FUSE>
 static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t st, LaunchInfo* info, bool select_only) {
   const int grid = (P.E + P.EPB - 1) / P.EPB;
@@ -262,11 +279,14 @@ static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t
   if constexpr (FUSE != 0) {
     // the fast obs path, decided per launch (step_fuse.h); the instances with the
     // compile-time control frequency are the ones launch_one picks under `fixed_cf`
-    const bool fixed_cf = !(s.flags & QS_FLAG_CF2P) && s.pyb_freq == 240 &&
-                          s.ctrl_freq == (s.task == QS_TASK_SPIRAL ? 48 : 30);
+    const bool fixed_cf = fixed_ctrl_freq(s);
     const void* obs[qs::kMaxFuse];
     for (int j = 0; j < P.nsteps; ++j) obs[j] = P.io[j].obs;
     P.obs_pipe = qs::obs_pipe_ok(fixed_cf, P.stage_rows, P.EPB * P.D, P.O, obs, P.nsteps) ? 1 : 0;
+  }
+  if constexpr (FUSE == 2) {
+    lds = seq_lds_base(h, lds) + (size_t)P.nsteps * qs::kSeqStepBytes * (size_t)h->dims.act_dim;
+    if (lds + kLdsStatic > kLdsBytes) return fail(QS_E_INVALID, "launch: the steps' action rows do not fit in LDS");
   }
   const void* fn = nullptr;
   bool ok;
@@ -276,6 +296,8 @@ static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t
   else if (s.task == QS_TASK_SPIRAL)
     ok = qs::launch_task<T, QS_TASK_SPIRAL, FUSE>(s.act_type, grid, lds, st, P, s.ctrl_freq, s.pyb_freq, s.physics, &fn,
                                                   select_only);
+  else if constexpr (FUSE == 2)
+    return fail(QS_E_INVALID, "launch: no action-sequence instances of the Flock / Meetup / LeaderFollower family");
   else
     ok = qs::launch_task<T, qs::kTaskMarl, FUSE>(s.act_type, grid, lds, st, P, s.ctrl_freq, s.pyb_freq, s.physics, &fn,
                                                  select_only);
@@ -290,6 +312,31 @@ static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t
 template <class T> static int launch_many(qs_handle* h, qs::ParamsMany<T>& P, hipStream_t st, LaunchInfo* info = nullptr,
                                           bool select_only = false) {
   return launch_kernel<T, 1>(h, P, st, info, select_only);
+}
+
+// Steps per launch of qs_step_seq: the handle's depth, capped where the action
+// rows (LDS, step_fuse.h seq_depth_cap) would not leave the launch's workgroups
+// resident at once.
+static constexpr size_t kSeqLdsMax = 64 * 1024;
+static int seq_depth(const qs_handle* h) {
+  if (h->rq) return 1;   // the search launch sits between two steps of an env
+  // Flock / Meetup / LeaderFollower: the multi-step instances of this family form
+  // the env reward with other division / square-root expansions than the single
+  // step (1 ulp apart), and qs_step_seq promises the single
+  // steps' bits: single steps, and no FUSE = 2 instances of the family are built
+  if (h->spec.task != QS_TASK_MULTIHOVER && h->spec.task != QS_TASK_SPIRAL) return 1;
+  const int epb = envs_per_wave(h);
+  const int grid = (h->spec.num_envs + epb - 1) / epb;
+  const int resident = std::max(1, std::min((grid + h->num_cu - 1) / h->num_cu, 32));
+  int stage_rows = 0;
+  size_t plan = 0;
+  if (lds_plan(h->dims, epb, resident, &stage_rows, &plan) != QS_OK) return 1;
+  const size_t used = kLdsStatic + kLdsGrain + seq_lds_base(h, plan);
+  // (a workgroup of these launches stays within kSeqLdsMax in all: none of the
+  // project's measured launches has asked for more)
+  const size_t share = std::min(kLdsBytes / (size_t)resident, kSeqLdsMax);
+  return qs::seq_depth_cap(share > used ? share - used : 0, kSeqLdsMax > used ? kSeqLdsMax - used : 0, h->dims.act_dim,
+                           h->fuse_depth);
 }
 
 template <class T> static int launch(qs_handle* h, qs::Params<T>& P, hipStream_t st, LaunchInfo* info = nullptr) {
@@ -470,6 +517,43 @@ template <class T> static int step_many_impl(qs_handle* h, int n, const qs_step_
     }
     if (rc != QS_OK) return rc;
     j += g.count;
+  }
+  return QS_OK;
+}
+
+// qs_step_seq with actions: the longest runs of steps that may share a launch
+// (step_fuse.h, SeqGroup), each run one launch of the FUSE = 2 instance; a run of
+// one step is the single-step launch.
+template <class T> static int step_seq_impl(qs_handle* h, int n, const float* const* actions, const qs_step_out* outs,
+                                            hipStream_t st) {
+  const int depth = seq_depth(h);
+  size_t sizes[qs::kFuseOuts];
+  out_sizes(h, sizes);
+  const size_t act_bytes = sizes[6];   // N·A·4, as actions_out
+  for (int j = 0; j < n;) {
+    qs::SeqGroup g;
+    g.begin(sizes, to_outs(outs[j]), actions[j], act_bytes);
+    while (j + g.count() < n && g.can_append(to_outs(outs[j + g.count()]), actions[j + g.count()], depth))
+      g.append(to_outs(outs[j + g.count()]), actions[j + g.count()]);
+    const int cnt = g.count();
+    int rc;
+    if (cnt > 1) {
+      qs::ParamsSeq<T> P;
+      std::memset(&P, 0, sizeof(P));
+      single_step_params<T>(h, P, nullptr, outs[j]);
+      P.nsteps = cnt;
+      for (int k = 0; k < cnt; ++k) {
+        P.io[k] = to_io<T>(outs[j + k]);
+        P.act[k] = actions[j + k];
+      }
+      rc = launch_kernel<T, 2>(h, P, st, nullptr, false);
+    } else {
+      qs::Params<T> P;
+      single_step_params<T>(h, P, actions[j], outs[j]);
+      rc = launch<T>(h, P, st);
+    }
+    if (rc != QS_OK) return rc;
+    j += cnt;
   }
   return QS_OK;
 }
@@ -711,6 +795,26 @@ int qs_step_many(qs_handle* h, int n, const qs_step_out* outs, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (h->dims.precision == 8) return step_many_impl<double>(h, n, outs, st);
   return step_many_impl<float>(h, n, outs, st);
+}
+
+int qs_step_seq(qs_handle* h, int n, const float* const* actions, const qs_step_out* outs, void* stream) {
+  if (!h) return fail(QS_E_INVALID, "qs_step_seq: null handle");
+  if (n < 0 || (n > 0 && !outs)) return fail(QS_E_INVALID, "qs_step_seq: bad argument");
+  if (!h->reset_done) return fail(QS_E_STATE, "qs_step_seq: call qs_reset first");
+  if (actions) {
+    for (int j = 0; j < n; ++j)
+      if (!actions[j])
+        return fail(QS_E_INVALID, "qs_step_seq: actions[" + std::to_string(j) + "] is null (every step reads its "
+                                  "actions or none does: pass actions = NULL for the random policy)");
+  }
+  h->fuse.forget();
+  hipStream_t st = (hipStream_t)stream;
+  if (!actions) {
+    if (h->dims.precision == 8) return step_many_impl<double>(h, n, outs, st);
+    return step_many_impl<float>(h, n, outs, st);
+  }
+  if (h->dims.precision == 8) return step_seq_impl<double>(h, n, actions, outs, st);
+  return step_seq_impl<float>(h, n, actions, outs, st);
 }
 
 // qs_state_io's view of the per-env records: counters as [QS_ENV_FIELDS][E]

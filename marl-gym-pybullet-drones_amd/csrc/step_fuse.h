@@ -109,4 +109,71 @@ struct FuseGroup {
   }
 };
 
+// A multi-step launch whose steps read caller-supplied actions (qs_step_seq).
+// The kernel reads the action rows of all its steps before the first step
+// runs, and its waves are at different steps at the same moment, so on top of
+// FuseGroup's rule a step joins only if
+//  - its action range is disjoint from every non-null output range of every
+//    step already in the group (else it would read what an earlier step of the
+//    launch has yet to write), and
+//  - each of its non-null output ranges is disjoint from the action range of
+//    every step already in the group (reads, once a launch runs, come first).
+// Cutting the launch before such a step restores the order of single steps.
+// Steps that read the same or overlapping actions may share a launch (nobody
+// writes them), and a step's own actions against its own outputs are what they
+// are for a single step.
+struct SeqGroup {
+  FuseGroup g;
+  size_t act_bytes = 0;              // N·A·4: the bytes of an action buffer a step reads
+  const void* acts[kFuseMax];
+
+  int count() const { return g.count; }
+
+  void begin(const size_t sizes[kFuseOuts], const FuseOuts& o, const void* act, size_t act_size) {
+    g.begin(sizes, o);
+    act_bytes = act_size;
+    acts[0] = act;
+  }
+
+  bool can_append(const FuseOuts& o, const void* act, int depth) const {
+    if (!g.can_append(o, depth)) return false;
+    for (int s = 0; s < g.count; ++s) {
+      for (int j = 0; j < kFuseOuts; ++j)
+        if (g.outs[s].p[j] && FuseGroup::overlap(act, act_bytes, g.outs[s].p[j], g.bytes[j])) return false;
+      for (int i = 0; i < kFuseOuts; ++i)
+        if (o.p[i] && FuseGroup::overlap(o.p[i], g.bytes[i], acts[s], act_bytes)) return false;
+    }
+    return true;
+  }
+
+  void append(const FuseOuts& o, const void* act) {
+    acts[g.count] = act;
+    g.append(o);
+  }
+};
+
+// The depth of such a launch.  Its action rows wait in LDS, kSeqStepBytes · A
+// bytes per step and one-wave workgroup ([step][component][lane] dwords), beside
+// the obs stage.  `share_free`: what a workgroup's share of the CU's LDS has left
+// when the launch's workgroups are all to be resident at once; `cu_free`: what is
+// left when a workgroup may take the whole CU's.  Residency is worth more than
+// depth (a grid that runs in two rounds pays every step twice), but below
+// kSeqMinDepth steps a launch has little left to share, so that many are taken
+// from `cu_free` where they fit.  Never more than `depth` or kFuseMax, never
+// fewer than 1 (= a single step, which reads its actions from HBM).
+constexpr int kSeqStepBytes = kObsPipeRows * 4;
+constexpr int kSeqMinDepth = 4;
+inline int seq_depth_cap(size_t share_free, size_t cu_free, int act_dim, int depth) {
+  const size_t per_step = (size_t)kSeqStepBytes * (size_t)(act_dim > 0 ? act_dim : 1);
+  size_t k = share_free / per_step;
+  if (k < (size_t)kSeqMinDepth) {
+    const size_t kc = cu_free / per_step;
+    const size_t floor_k = kc < (size_t)kSeqMinDepth ? kc : (size_t)kSeqMinDepth;
+    if (floor_k > k) k = floor_k;
+  }
+  const size_t cap = (size_t)(depth < kFuseMax ? depth : kFuseMax);
+  if (k > cap) k = cap;
+  return k < 1 ? 1 : (int)k;
+}
+
 }  // namespace qs

@@ -304,7 +304,14 @@ template <class T> struct ParamsMany : Params<T> {
   int obs_pipe;
   StepIO<T> io[kMaxFuse];
 };
-template <class T, int FUSE> using KernelParams = std::conditional_t<FUSE != 0, ParamsMany<T>, Params<T>>;
+// Arguments of the multi-step instances that read caller-supplied actions
+// (step_kernel FUSE = 2): step j consumes act[j] ([N][A] float32, 4-byte
+// aligned).  Again a type of its own: Params and ParamsMany keep their size.
+template <class T> struct ParamsSeq : ParamsMany<T> {
+  const float* act[kMaxFuse];
+};
+template <class T, int FUSE>
+using KernelParams = std::conditional_t<FUSE == 2, ParamsSeq<T>, std::conditional_t<FUSE != 0, ParamsMany<T>, Params<T>>>;
 
 // ---------------------------------------------------- conversions (external)
 // pybullet getMatrixFromQuaternion = btMatrix3x3::setRotation (s = 2/|q|²).
@@ -803,6 +810,12 @@ template <class T> __device__ __forceinline__ bool launch_obs_pipe(const ParamsM
 // per-env reduction and flags stay inside the wave.
 // Bit-identical to P.nsteps launches of the FUSE = 0 instance (no loop is
 // emitted for that one).
+// FUSE = 2: the same loop over caller-supplied actions (ParamsSeq::act[j] for
+// step j).  The action rows of every step of the launch go into LDS with the
+// launch's other loads ([step][component][lane] dwords by LDS-DMA, so a 4-byte
+// aligned buffer will do), and a step takes its row from there where FUSE = 1
+// draws: the loop still issues no global load.  Everything else is the shared
+// body.
 template <class T, int TASK, int ACT, int CF, int PHYS, int AUXM, int FUSE = 0>
 __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   using F = M<T>;
@@ -917,9 +930,13 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   // Otherwise it goes into LDS by LDS-DMA, lane-linear [slot][lane][A] (A = 3
   // as [slot][k][lane]: a dwordx3 DMA does not land lane-linear at 12 B).
   extern __shared__ float4 dyn_lds4[];   // float4: 16-B aligned staging for the obs stores
+  // FUSE = 2: the launch's action rows come first, nsteps · A · kBlock floats
+  // (a multiple of 256 bytes: the stage keeps its alignment)
+  constexpr bool kSeq = FUSE == 2;
   float* const dyn_lds = reinterpret_cast<float*>(dyn_lds4);
-  float* const hist_pref = dyn_lds;
-  float* const stage = dyn_lds + (CF ? 0 : (size_t)H * kBlock * A);
+  float* const act_lds = dyn_lds;
+  float* const hist_pref = kSeq ? dyn_lds + (size_t)launch_steps(P) * kBlock * A : dyn_lds;
+  float* const stage = kSeq ? hist_pref + (CF ? 0 : (size_t)H * kBlock * A) : dyn_lds + (CF ? 0 : (size_t)H * kBlock * A);
   constexpr int HR = CF ? CF / 2 : 1;
   float hreg[HR][A];
   if constexpr (CF != 0) {
@@ -947,6 +964,20 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
       } else {
         __builtin_amdgcn_global_load_lds((g_ptr_t)src, (lds_ptr_t)(hist_pref + sl * kBlock * 4), 16, 0, QS_HIST_DMA_AUX);
       }
+    }
+  }
+  // FUSE = 2: every step's action row of this lane, [step][component][lane] in
+  // LDS, a dword per DMA (the buffers are only 4-byte aligned; a row's A dwords
+  // share their cache lines).  Idle lanes read the workgroup's first row, which
+  // exists: nothing out of range, and nothing uses what they read.
+  if constexpr (kSeq) {
+    const int a_src = valid ? a : blockIdx.x * P.EPB * D;
+    const int ns = launch_steps(P);
+    for (int j = 0; j < ns; ++j) {
+      const float* src = P.act[j] + (size_t)a_src * A;
+#pragma unroll
+      for (int k = 0; k < A; ++k)
+        __builtin_amdgcn_global_load_lds((g_ptr_t)(src + k), (lds_ptr_t)(act_lds + (j * A + k) * kBlock), 4, 0, 0);
     }
   }
   auto hist_at = [&](int sl, int k) -> float {   // LDS image (CF == 0): ring slot sl, component k, this lane
@@ -1056,7 +1087,10 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     done_env = false;
   }
   // ---------------- action (trainer-provided or synthetic random policy)
-  if (mode == MODE_STEP) {
+  if constexpr (kSeq) {   // step ks's row of this lane (in LDS since before the loop)
+#pragma unroll
+    for (int k = 0; k < A; ++k) cur_act[k] = act_lds[(ks * A + k) * kBlock + tid];
+  } else if (mode == MODE_STEP) {
     if (!kFuse && P.act_in) {
 #pragma unroll
       for (int k = 0; k < A; ++k) cur_act[k] = act_in[k];

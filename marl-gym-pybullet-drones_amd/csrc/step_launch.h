@@ -7,7 +7,8 @@ namespace qs {
 // from cf/pf/ph).  Defined and explicitly instantiated in one translation unit
 // per task family.  Returns false for an unknown action type.
 // FUSE = 1: the multi-step instances (ParamsMany: P.nsteps steps per launch,
-// P.io[]), in translation units of their own.  `fn`, if given, receives the kernel's
+// P.io[]), in translation units of their own; FUSE = 2: those that read the
+// steps' actions from ParamsSeq::act[], in further ones.  `fn`, if given, receives the kernel's
 // function pointer (what a graph kernel node names); `select_only` looks the
 // kernel up without launching it.
 template <class T, int TASK, int FUSE = 0>

@@ -60,7 +60,7 @@ EPISODE_DTYPE = np.dtype([("ret", "<f8"), ("len", "<i4"), ("env", "<i4"), ("seq"
 # Every symbol include/quadswarm.h declares (tests check the .so exports them).
 ABI_VERSION = 4   # include/quadswarm.h QS_ABI_VERSION
 EXPORTS = ("qs_create", "qs_destroy", "qs_last_error", "qs_abi_version", "qs_get_dims", "qs_reset",
-           "qs_reset_envs", "qs_step", "qs_step_many", "qs_state_io", "qs_episode_log", "qs_reset_error", "qs_calib_copy",
+           "qs_reset_envs", "qs_step", "qs_step_many", "qs_step_seq", "qs_state_io", "qs_episode_log", "qs_reset_error", "qs_calib_copy",
            # include/qs_learner.h
            "qs_gae", "qs_adam_gated", "qs_adam_commit", "qs_ppo_heads", "qs_ppo_heads_work_bytes",
            "qs_mlp_bias_tanh", "qs_mlp_bwd_blocks", "qs_mlp_tanh_bwd", "qs_mlp_sum_partials",
@@ -121,6 +121,7 @@ def load():
     L.qs_reset_envs.argtypes = [vp, vp, vp, vp]
     L.qs_step.argtypes = [vp, vp, ctypes.POINTER(QsStepOut), vp]
     L.qs_step_many.argtypes = [vp, i32, ctypes.POINTER(QsStepOut), vp]
+    L.qs_step_seq.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(QsStepOut), vp]
     L.qs_state_io.argtypes = [vp, i32, vp, i32, vp]
     L.qs_episode_log.argtypes = [vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
     L.qs_reset_error.argtypes = [vp, ctypes.POINTER(i32)]

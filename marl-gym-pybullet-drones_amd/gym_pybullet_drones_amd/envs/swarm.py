@@ -192,10 +192,7 @@ class QuadSwarm:
         """One control step of every env.  actions: (E, D, A) float32 on device, or None
         for the synthetic random policy (Philox U(-1,1))."""
         if actions is not None:
-            if (actions.dtype != torch.float32 or not actions.is_contiguous() or actions.device != self.device
-                    or actions.numel() != self.num_agents * self.act_dim):
-                raise ValueError(f"actions must be a contiguous float32 ({self.num_envs},{self.num_drones},"
-                                 f"{self.act_dim}) tensor on {self.device}")
+            self._check_actions(actions)
         so, res = self._step_out(obs, reward, terminated, truncated, terminal_obs, reasons, actions_out,
                                  want_terminal, want_reasons)
         L.check(self.lib.qs_step(self._h, L.ptr(actions), ctypes.byref(so), self._stream()), "qs_step")
@@ -223,16 +220,45 @@ class QuadSwarm:
                          L.ptr(reasons), L.ptr(actions_out))
         return so, StepResult(obs, reward, terminated, truncated, terminal_obs, reasons, actions_out)
 
-    def step_many(self, outs):
-        """len(outs) consecutive control steps under the synthetic random policy, as
-        `step(None, **outs[j])` for each j, but several steps to a launch with the
-        envs' state kept on-chip in between (qs_step_many; the depth is
-        QS_MAX_FUSED_STEPS at construction).  outs: one dict of step()'s output
-        keywords per step; steps share a launch only while their buffers are
-        distinct.  Returns the steps' StepResults."""
+    def _check_actions(self, actions):
+        if (actions.dtype != torch.float32 or not actions.is_contiguous() or actions.device != self.device
+                or actions.numel() != self.num_agents * self.act_dim):
+            raise ValueError(f"actions must be a contiguous float32 ({self.num_envs},{self.num_drones},"
+                             f"{self.act_dim}) tensor on {self.device}")
+
+    def step_many(self, outs, actions=None):
+        """len(outs) consecutive control steps, as `step(actions[j], **outs[j])` for
+        each j, but several steps to a launch with the envs' state kept on-chip in
+        between (the depth is QS_MAX_FUSED_STEPS at construction).  outs: one dict
+        of step()'s output keywords per step.  actions: None for the synthetic
+        random policy (qs_step_many), or the steps' actions (qs_step_seq) as a list
+        of len(outs) (E, D, A) tensors or one (len(outs), E, D, A) tensor, whose
+        slices are passed as they are (no copy).  Steps share a launch only while
+        their output buffers are distinct and none of them reads as actions what
+        another one writes; otherwise the launch is cut, so the result always
+        equals the single steps'.  Returns the steps' StepResults."""
+        n = len(outs)
+        acts = None
+        if actions is not None:
+            if isinstance(actions, torch.Tensor):
+                if actions.dim() < 1 or actions.shape[0] != n:
+                    raise ValueError(f"actions must hold {n} steps: ({n},{self.num_envs},{self.num_drones},{self.act_dim})")
+                acts = [actions[j] for j in range(n)]
+            else:
+                acts = list(actions)
+                if len(acts) != n:
+                    raise ValueError(f"actions must hold {n} steps, one tensor each")
+            for a in acts:
+                if not isinstance(a, torch.Tensor):
+                    raise ValueError("actions: every step needs its tensor (None for all of them draws the random policy)")
+                self._check_actions(a)
         recs = [self._step_out(**kw) for kw in outs]
-        arr = (L.QsStepOut * max(1, len(recs)))(*[so for so, _ in recs])
-        L.check(self.lib.qs_step_many(self._h, len(recs), arr, self._stream()), "qs_step_many")
+        arr = (L.QsStepOut * max(1, n))(*[so for so, _ in recs])
+        if acts is None:
+            L.check(self.lib.qs_step_many(self._h, n, arr, self._stream()), "qs_step_many")
+        else:
+            ptrs = (ctypes.c_void_p * max(1, n))(*[a.data_ptr() for a in acts])
+            L.check(self.lib.qs_step_seq(self._h, n, ptrs, arr, self._stream()), "qs_step_seq")
         return [res for _, res in recs]
 
     # ------------------------------------------------------------ state I/O

@@ -105,6 +105,7 @@ class SwarmVecEnv(VecEnv):
         self.seed = int(seed)
         super().__init__(num_envs, observation_space_for(self.swarm), action_space_for(self.swarm))
         self._actions = None
+        self._rollout_bufs = {}   # rollout_t's output buffers, by step count
         self.NUM_DRONES = self.swarm.num_drones
         self.CTRL_FREQ = self.swarm.ctrl_freq
         self.CTRL_TIMESTEP = 1.0 / self.CTRL_FREQ
@@ -164,6 +165,33 @@ class SwarmVecEnv(VecEnv):
 
     def step_t(self, actions=None, **kw):
         return self.swarm.step(actions, **kw)
+
+    def rollout_t(self, actions, **bufs):
+        """`actions.shape[0]` control steps over the (n, E, D, A) device tensor
+        `actions`, as step_t(actions[j]) for each j but several steps to a launch
+        (QuadSwarm.step_many).  Returns the stacked (obs[n, E, D, O], reward[n, E],
+        terminated[n, E], truncated[n, E]); no info dicts, no host sync.  The
+        buffers are allocated once per n and returned again by every later call
+        of the same n; `bufs` may name the caller's own (obs=, reward=, terminated=,
+        truncated=, and step()'s optional outputs, each stacked over n)."""
+        sw = self.swarm
+        if actions.dim() != 4:
+            raise ValueError(f"actions must be a (n, {sw.num_envs}, {sw.num_drones}, {sw.act_dim}) tensor")
+        n = actions.shape[0]
+        own = self._rollout_bufs.get(n)
+        if own is None:
+            kw = dict(device=sw.device)
+            own = dict(obs=torch.zeros((n, sw.num_envs, sw.num_drones, sw.obs_dim), dtype=torch.float32, **kw),
+                       reward=torch.zeros((n, sw.num_envs), dtype=sw.rdtype, **kw),
+                       terminated=torch.zeros((n, sw.num_envs), dtype=torch.uint8, **kw),
+                       truncated=torch.zeros((n, sw.num_envs), dtype=torch.uint8, **kw))
+            self._rollout_bufs[n] = own
+        out = {**own, **bufs}
+        for k, v in out.items():
+            if v.shape[0] != n:
+                raise ValueError(f"{k} must be stacked over the {n} steps")
+        sw.step_many([{k: v[j] for k, v in out.items()} for j in range(n)], actions=actions)
+        return out["obs"], out["reward"], out["terminated"], out["truncated"]
 
     # -------------------------------------------- checkpoint RNG (MP:203-270)
     def get_env_random_state(self):
