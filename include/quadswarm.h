@@ -277,6 +277,20 @@ int qs_step_many(qs_handle* h, int n, const qs_step_out* outs, void* stream);
 int qs_step_seq(qs_handle* h, int n, const float* const* actions,
                 const qs_step_out* outs, void* stream);
 
+/* Multi-step launches this handle has made so far (host, no device work):
+ * out[0] on the general multi-step kernel instances, out[1] on the
+ * shape-specialised one.  The specialised instance serves synthetic-policy
+ * launches of two or more steps of MultiHover, ONE_D_PID at 30 / 240 Hz with no
+ * extra forces and CF2X, 8 drones, a multiple of 8 envs, a reject-free layout,
+ * auto-reset on, and at every step of the launch 16-byte aligned obs, reward,
+ * terminated, truncated and actions_out and neither terminal_obs nor reasons;
+ * every other launch, and every launch of a process with QS_HOT_SHAPE=0 in its
+ * environment at qs_create, runs the general instances.  Results do not
+ * depend on which one runs.  The kernel node that qs_step calls build on a
+ * capturing stream counts once, under the instance it names when the capture
+ * ends.  (A new entry point of ABI 4, like qs_step_seq.) */
+int qs_launch_counts(const qs_handle* h, int64_t out[2]);
+
 /* Copy a state block between the handle and `buf` (device pointer).
  * dir = 0: handle → buf (get), dir = 1: buf → handle (set). */
 int qs_state_io(qs_handle* h, int block, void* buf, int dir, void* stream);

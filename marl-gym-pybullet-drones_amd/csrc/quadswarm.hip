@@ -2,8 +2,9 @@
 // include/quadswarm.h (handle, state buffers, launches).  The device code is
 // csrc/step_kernel.h; the kernels are instantiated per task family in
 // step_mh.hip / step_spiral.hip / step_marl.hip (single step), their
-// *_fused.hip twins (several control steps per launch) and step_mh_seq.hip /
-// step_spiral_seq.hip (the same over caller-supplied actions).
+// *_fused.hip twins (several control steps per launch), step_mh_seq.hip /
+// step_spiral_seq.hip (the same over caller-supplied actions) and step_mh_hot.hip
+// (MultiHover's shape-specialised multi-step instances).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -23,6 +24,11 @@ static_assert(qs::kFuseMax == qs::kMaxFuse, "step_fuse.h and step_kernel.h disag
 static_assert(qs::kObsPipeMaxRow == qs::kObsPipeMaxO && qs::kObsPipeRows == qs::kBlock,
               "step_fuse.h and step_kernel.h disagree on the fast obs path's shape");
 static_assert(qs::kSeqStepBytes == qs::kBlock * (int)sizeof(float), "step_fuse.h and step_kernel.h disagree on an action row's LDS");
+static_assert(qs::kHotTask == QS_TASK_MULTIHOVER && qs::kHotAct == QS_ACT_ONE_D_PID && qs::kHotPhysA == QS_PHYS_PYB &&
+                  qs::kHotPhysB == QS_PHYS_DYN && qs::kHotBadFlags == (QS_FLAG_NO_AUTORESET | QS_FLAG_CF2P),
+              "step_fuse.h restates quadswarm.h's values for the hot shape");
+static_assert(qs::kHotDrones == qs::kHotD && qs::kHotEnvs == qs::kBlock / qs::kHotD && qs::kFuseOuts == 7,
+              "step_fuse.h and step_kernel.h disagree on the hot shape");
 
 namespace qs {
 // Calibration kernel: dword per lane, grid-stride (MI355X_MICROARCH §HBM).
@@ -171,6 +177,15 @@ struct qs_handle {
   // ballots) where an env is 2, 4, 8 or 16 lanes; QS_WAVE_REDUCE=0 keeps them on the
   // LDS path (the A/B switch)
   bool wave_reduce = true;
+  // Multi-step launches of the shape qs::hot_shape_ok accepts run the specialised
+  // instance (step_mh_hot.hip); QS_HOT_SHAPE=0 keeps them on the general one (the
+  // A/B switch).  launches[]: multi-step launches made so far on the general [0]
+  // and on the specialised [1] instance (qs_launch_counts); a capture's kernel
+  // node counts once, under the instance it names after its last append
+  // (fuse_kind: which one that is for the node of h->fuse, -1 before it holds two steps).
+  bool hot_shape = true;
+  int64_t launches[2] = {0, 0};
+  int fuse_kind = -1;
   qs::FuseGroup fuse;
   qs::ParamsMany<float> fuse_pf;
   qs::ParamsMany<double> fuse_pd;
@@ -270,7 +285,8 @@ struct LaunchInfo {
 // actions P.act[0 .. P.nsteps-1], whose rows take LDS of their own (the caller
 // has capped P.nsteps by seq_depth).  select_only: no launch.
 template <class T, int FUSE>
-static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t st, LaunchInfo* info, bool select_only) {
+static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t st, LaunchInfo* info, bool select_only,
+                         int* kind = nullptr) {
   const int grid = (P.E + P.EPB - 1) / P.EPB;
   size_t lds = 0;
   if (lds_plan(h->dims, P.EPB, (grid + h->num_cu - 1) / h->num_cu, &P.stage_rows, &lds) != QS_OK)
@@ -283,6 +299,29 @@ static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t
     const void* obs[qs::kMaxFuse];
     for (int j = 0; j < P.nsteps; ++j) obs[j] = P.io[j].obs;
     P.obs_pipe = qs::obs_pipe_ok(fixed_cf, P.stage_rows, P.EPB * P.D, P.O, obs, P.nsteps) ? 1 : 0;
+    if constexpr (FUSE == 1) {
+      // the shape-specialised instance, decided per launch over all its steps (so a
+      // capture's node is re-decided, either way, each time a step joins it)
+      unsigned masks[qs::kMaxFuse];
+      for (int j = 0; j < P.nsteps; ++j) {
+        const qs::StepIO<T>& o = P.io[j];
+        masks[j] = qs::out_mask(qs::FuseOuts{{o.obs, o.rew, o.term, o.trunc, o.tobs, o.reasons, o.act_out}});
+      }
+      const qs::HotShape hs{s.task, s.act_type, fixed_cf, s.physics, s.aux_forces, s.flags, P.D, P.E, P.EPB,
+                            P.reject_free != 0, P.reset_queue != nullptr, P.reset_pre != nullptr, P.wave_reduce != 0,
+                            P.obs_pipe != 0};
+      const bool hot = h->hot_shape && qs::hot_shape_ok(hs, masks, P.nsteps);
+      if (kind) *kind = hot ? 1 : 0;
+      if (hot) {
+        const void* fn = nullptr;
+        qs::launch_hot<T>(s.physics, grid, lds, st, P, &fn, select_only);
+        if (info) { info->fn = fn; info->grid = grid; info->lds = lds; }
+        if (select_only) return QS_OK;
+        HIP_TRY(hipGetLastError());
+        h->launches[1] += 1;
+        return QS_OK;
+      }
+    }
   }
   if constexpr (FUSE == 2) {
     lds = seq_lds_base(h, lds) + (size_t)P.nsteps * qs::kSeqStepBytes * (size_t)h->dims.act_dim;
@@ -305,13 +344,15 @@ static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t
   if (info) { info->fn = fn; info->grid = grid; info->lds = lds; }
   if (select_only) return QS_OK;
   HIP_TRY(hipGetLastError());
+  if constexpr (FUSE == 1) h->launches[0] += 1;
   return QS_OK;
 }
 
-// A launch of P.nsteps (>= 2) control steps.
+// A launch of P.nsteps (>= 2) control steps.  `kind`, if given, receives the
+// instance chosen: 0 general, 1 shape-specialised.
 template <class T> static int launch_many(qs_handle* h, qs::ParamsMany<T>& P, hipStream_t st, LaunchInfo* info = nullptr,
-                                          bool select_only = false) {
-  return launch_kernel<T, 1>(h, P, st, info, select_only);
+                                          bool select_only = false, int* kind = nullptr) {
+  return launch_kernel<T, 1>(h, P, st, info, select_only, kind);
 }
 
 // Steps per launch of qs_step_seq: the handle's depth, capped where the action
@@ -443,7 +484,8 @@ template <class T> static bool try_coalesce(qs_handle* h, const qs_step_out& o, 
   P.io[g.count] = to_io<T>(o);
   P.nsteps = g.count + 1;
   LaunchInfo li;
-  if (launch_many(h, P, st, &li, /*select_only=*/true) != QS_OK || !li.fn) return false;
+  int kind = 0;
+  if (launch_many(h, P, st, &li, /*select_only=*/true, &kind) != QS_OK || !li.fn) return false;
   hipKernelNodeParams np;
   std::memset(&np, 0, sizeof(np));
   void* args[1] = {&P};
@@ -455,6 +497,10 @@ template <class T> static bool try_coalesce(qs_handle* h, const qs_step_out& o, 
   if (hipGraphKernelNodeSetParams(node, &np) != hipSuccess) { (void)hipGetLastError(); return false; }
   fuse_params<T>(h) = P;
   g.append(fo);
+  // the node now names instance `kind`: it counts there, and no longer where it did
+  if (h->fuse_kind >= 0) h->launches[h->fuse_kind] -= 1;
+  h->launches[kind] += 1;
+  h->fuse_kind = kind;
   return true;
 }
 
@@ -475,6 +521,7 @@ template <class T> static void note_capture(qs_handle* h, const qs::Params<T>& P
   size_t sizes[qs::kFuseOuts];
   out_sizes(h, sizes);
   h->fuse.begin(sizes, to_outs(o), c.id, (void*)st, (void*)c.deps[0]);
+  h->fuse_kind = -1;   // a single step so far
   qs::ParamsMany<T>& F = fuse_params<T>(h);
   std::memset(&F, 0, sizeof(F));
   static_cast<qs::Params<T>&>(F) = P;
@@ -616,6 +663,7 @@ int qs_create(const qs_spec* spec, int device, qs_handle** out) {
     if (end != v) h->fuse_depth = (int)std::min<long>(std::max<long>(k, 1), qs::kMaxFuse);
   }
   if (const char* v = getenv("QS_WAVE_REDUCE")) h->wave_reduce = std::strtol(v, nullptr, 10) != 0;   // read once, here
+  if (const char* v = getenv("QS_HOT_SHAPE")) h->hot_shape = std::strtol(v, nullptr, 10) != 0;       // read once, here
   h->spec = s;
   h->spec.initial_xyzs = nullptr;
   h->device = device;
@@ -727,6 +775,13 @@ int qs_destroy(qs_handle* h) {
   void* ptrs[] = {h->st, h->env, h->hist, h->orig, h->log, h->err, h->stamps, h->rq, h->rpre, h->logw, h->log_sel};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   delete h;
+  return QS_OK;
+}
+
+int qs_launch_counts(const qs_handle* h, int64_t out[2]) {
+  if (!h || !out) return fail(QS_E_INVALID, "qs_launch_counts: null argument");
+  out[0] = h->launches[0];
+  out[1] = h->launches[1];
   return QS_OK;
 }
 

@@ -45,6 +45,58 @@ inline bool obs_pipe_ok(bool fixed_cf, int stage_rows, int rows, int row_floats,
   return true;
 }
 
+// May a multi-step launch of the synthetic policy run the shape-specialised
+// kernel instance (step_kernel HOT = 1, step_mh_hot.hip)?  That instance has
+// folded in, as constants, everything listed here; a launch that differs in any
+// of it takes the general instance:
+//  - MultiHover, ONE_D_PID, the compile-time control frequency (`fixed_cf`:
+//    30 Hz at 240, not DroneModel.CF2P), DYN or PYB physics, no extra forces,
+//    auto-reset on (neither QS_FLAG_NO_AUTORESET nor QS_FLAG_CF2P set),
+//  - kHotDrones drones, kHotEnvs envs per workgroup and a number of envs that
+//    fills every workgroup (no idle lane anywhere in the grid),
+//  - a reject-free layout (a reset is try 0) and neither a deferred search queue
+//    nor precomputed searches,
+//  - the per-env reduction inside the wave (QS_WAVE_REDUCE) and the fast obs path
+//    (obs_pipe_ok's verdict for this launch, which covers the obs alignment),
+//  - at least two steps, and at every step of the launch the same outputs: obs,
+//    reward, terminated, truncated and actions_out present, terminal_obs and
+//    reasons absent (kHotOutMask over FuseOuts' order).
+// The values of quadswarm.h's enums are restated as plain ints (this header
+// stays free of it); quadswarm.hip checks them against the header's.
+constexpr int kHotTask = 0, kHotAct = 4;             // QS_TASK_MULTIHOVER, QS_ACT_ONE_D_PID
+constexpr int kHotPhysA = 0, kHotPhysB = 1;          // QS_PHYS_PYB, QS_PHYS_DYN
+constexpr unsigned kHotBadFlags = 1u | 4u;           // QS_FLAG_NO_AUTORESET | QS_FLAG_CF2P
+constexpr int kHotDrones = 8, kHotEnvs = 8;          // = kHotD, kBlock / kHotD (step_kernel.h)
+constexpr unsigned kHotOutMask = 1u | 2u | 4u | 8u | 64u;   // obs, reward, terminated, truncated, actions_out
+
+inline unsigned out_mask(const FuseOuts& o) {
+  unsigned m = 0;
+  for (int i = 0; i < kFuseOuts; ++i)
+    if (o.p[i]) m |= 1u << i;
+  return m;
+}
+
+struct HotShape {
+  int task, act_type;
+  bool fixed_cf;
+  int physics;
+  unsigned aux, flags;
+  int D, E, EPB;
+  bool reject_free, reset_queue, reset_pre, wave_reduce, obs_pipe;
+};
+
+inline bool hot_shape_ok(const HotShape& s, const unsigned* out_masks, int nsteps) {
+  if (s.task != kHotTask || s.act_type != kHotAct || !s.fixed_cf) return false;
+  if (s.physics != kHotPhysA && s.physics != kHotPhysB) return false;
+  if (s.aux != 0 || (s.flags & kHotBadFlags) != 0) return false;
+  if (s.D != kHotDrones || s.EPB != kHotEnvs || s.E <= 0 || s.E % s.EPB != 0) return false;
+  if (!s.reject_free || s.reset_queue || s.reset_pre || !s.wave_reduce || !s.obs_pipe) return false;
+  if (nsteps < 2 || nsteps > kFuseMax || !out_masks) return false;
+  for (int j = 0; j < nsteps; ++j)
+    if (out_masks[j] != kHotOutMask) return false;
+  return true;
+}
+
 struct FuseGroup {
   bool live = false;
   unsigned long long capture_id = 0;   // the stream capture the node belongs to

@@ -510,6 +510,17 @@ __device__ __forceinline__ void reset_candidate(const Params<T>& P, const T orig
   py = F::add_rn(orig[1], n1);
   pz = clampv(F::add_rn(orig[2], n2), T(0.1), T(1.0));
 }
+// The same with the Philox keys as values (the hot shape holds them in registers).
+template <class T>
+__device__ __forceinline__ void reset_candidate(uint32_t k0, uint32_t k1, const T orig[3], int d, uint32_t try_idx,
+                                                uint32_t genv, uint32_t episode, T& px, T& py, T& pz) {
+  using F = M<T>;
+  U4 r = philox(U4{try_idx, genv, episode, (uint32_t)((STREAM_RESET << 24) | d)}, k0, k1);
+  T n0 = T(0.5) * u01<T>(r.x) - T(0.25), n1 = T(0.5) * u01<T>(r.y) - T(0.25), n2 = T(0.5) * u01<T>(r.z) - T(0.25);
+  px = F::add_rn(orig[0], n0);
+  py = F::add_rn(orig[1], n1);
+  pz = clampv(F::add_rn(orig[2], n2), T(0.1), T(1.0));
+}
 // MH:96-101 pair test: closer than 0.5 m (the same _rn operation order as the oracle).
 template <class T> __device__ __forceinline__ bool too_close(T ax, T ay, T az, T bx, T by, T bz) {
   using F = M<T>;
@@ -816,10 +827,56 @@ template <class T> __device__ __forceinline__ bool launch_obs_pipe(const ParamsM
 // aligned buffer will do), and a step takes its row from there where FUSE = 1
 // draws: the loop still issues no global load.  Everything else is the shared
 // body.
-template <class T, int TASK, int ACT, int CF, int PHYS, int AUXM, int FUSE = 0>
+// HOT = 1 (FUSE = 1, MultiHover, compile-time control frequency, AUXM 0 only):
+// the launch shape qs::hot_shape_ok (step_fuse.h) accepts, with everything that
+// predicate fixes for the launch folded in ("hot shape"): D = 8
+// drones, 8 envs in every workgroup (every lane a drone: no `valid`), the per-env
+// reduction inside the wave, the fast obs path, obs / reward / terminated /
+// truncated / actions_out written and terminal_obs / reasons absent at every
+// step, reject-free resets (try 0 is the reset: no search, no queue) with
+// auto-reset on; the launch's scalars read once before the loop, and everything
+// that only happens when an env of the wave ends an episode (log record,
+// auto-reset, the reset lanes' PID attitude) behind wave-uniform tests of one
+// ballot.  No arithmetic differs: the same operations in the same order as
+// HOT = 0, whose statements stand as they were (each hot form is chosen by a
+// compile-time test beside the statement it replaces), so the other instances
+// compile to the code they had.
+// QS_HOT_ITEMS (dev builds): each bit keeps one of those pieces, to measure it by
+// leaving it out — 1 shape, 2 outputs, 4 resets, 8 hoisted scalars, 16 rare tail.
+#ifndef QS_HOT_ITEMS
+#define QS_HOT_ITEMS 31
+#endif
+constexpr int kHotD = 8;   // = qs::kHotDrones (step_fuse.h), checked in quadswarm.hip
+// A launch-invariant scalar the loop needs, read before it and held in an SGPR: as
+// a plain kernel-argument read the backend re-issues the scalar load inside the
+// loop (a load is cheaper to repeat than a register is to keep) and waits for it.
+template <class V> __device__ __forceinline__ V keep_sgpr(V v) {
+  __asm__ volatile("" : "+s"(v));
+  return v;
+}
+__device__ __forceinline__ float keep_sgpr(float v) {
+  return __builtin_bit_cast(float, keep_sgpr(__builtin_bit_cast(uint32_t, v)));
+}
+__device__ __forceinline__ double keep_sgpr(double v) {
+  return __builtin_bit_cast(double, keep_sgpr(__builtin_bit_cast(unsigned long long, v)));
+}
+template <class V> __device__ __forceinline__ V* keep_sgpr(V* p) {
+  return reinterpret_cast<V*>(keep_sgpr((unsigned long long)reinterpret_cast<uintptr_t>(p)));
+}
+
+template <class T, int TASK, int ACT, int CF, int PHYS, int AUXM, int FUSE = 0, int HOT = 0>
 __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   using F = M<T>;
   constexpr bool kFuse = FUSE != 0;
+  constexpr bool kHot = HOT != 0;
+  static_assert(!kHot || (FUSE == 1 && TASK == QS_TASK_MULTIHOVER && CF != 0 && AUXM == 0), "hot shape: see above");
+  constexpr bool kHotShape = kHot && (QS_HOT_ITEMS & 1) != 0, kHotOuts = kHot && (QS_HOT_ITEMS & 2) != 0;
+  constexpr bool kHotReset = kHot && (QS_HOT_ITEMS & 4) != 0, kHotScal = kHot && (QS_HOT_ITEMS & 8) != 0;
+  // (the tests are on the wave's ballot of `dn`, which the shape item's wave reduction forms)
+  constexpr bool kHotTail = kHotShape && (QS_HOT_ITEMS & 16) != 0;
+  // a launch value: hot shape, the copy read before the loop (name_h below); else P's, read where it is used
+#define QS_LAUNCH_VAL(field) (kHotScal ? field##_h : P.field)
+#define QS_EPB (kHotShape ? kBlock / kHotD : P.EPB)
   const int mode = kFuse ? (int)MODE_STEP : P.mode;
   constexpr bool kP = AUXM == 3;   // DroneModel.CF2P
   using MD = Model<kP>;
@@ -830,13 +887,13 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   constexpr bool kMarl = TASK == kTaskMarl;   // Flock / Meetup / LeaderFollower (P.task)
   __shared__ Shared<T> s;
   const int tid = threadIdx.x;
-  const int D = P.D, N = P.N;
+  const int D = kHotShape ? kHotD : P.D, N = kHotScal ? keep_sgpr(P.N) : P.N;
   const int H = CF ? CF / 2 : P.H;
   const int S = qs_dev::kNoCompute ? 0 : (CF ? 240 / CF : P.S);
   const int O = CF ? 12 + (CF / 2) * A + (kSpiral ? 11 : 0) : P.O;
   const int lenv = tid / D, d = tid - lenv * D;
-  const int e = blockIdx.x * P.EPB + lenv;
-  const bool valid = (lenv < P.EPB) && (e < P.E);
+  const int e = blockIdx.x * QS_EPB + lenv;
+  const bool valid = kHotShape ? true : ((lenv < P.EPB) && (e < P.E));
   const int a = e * D + d;
   const uint32_t genv = (uint32_t)(P.env_offset + e);
   // kBlock == 64 is one wave: an env of 2, 4, 8 or 16 drones lies inside one
@@ -845,7 +902,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   // single step (bound by its loads and stores, its waits counted exactly by the
   // compiler) ran 9.00 µs against 8.84 (C3; 8.91 as it is)
   static_assert(kBlock == 64, "the wave reduction assumes one wave per workgroup");
-  const bool wave_red = kFuse && !kMarl && P.wave_reduce != 0 && (D == 2 || D == 4 || D == 8 || D == 16);
+  const bool wave_red = kHotShape ? true : (kFuse && !kMarl && P.wave_reduce != 0 && (D == 2 || D == 4 || D == 8 || D == 16));
   SoA<T> SA;
   SA.rsrc = __builtin_amdgcn_make_buffer_rsrc(P.st, 0, (int)((unsigned)QS_AGENT_FIELDS * (unsigned)N * sizeof(T)), 0x00020000);
   SA.fstride = (unsigned)N * (unsigned)sizeof(T);
@@ -1059,7 +1116,16 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   constexpr int kPipeTail = kSpan4 - (kPipeIt - 1) * kBlock;    // lanes of the last piece
   bool pipe = false;             // workgroup-uniform
   float* pend = nullptr;         // workgroup-uniform: the span the stage is waiting to go to
-  if constexpr (kPipe) pipe = launch_obs_pipe(P) && P.EPB * D == kBlock && (int)blockIdx.x * P.EPB + P.EPB <= P.E;
+  if constexpr (kPipe) pipe = kHotShape ? true : (launch_obs_pipe(P) && P.EPB * D == kBlock && (int)blockIdx.x * P.EPB + P.EPB <= P.E);
+  static_assert(!kHot || kPipe, "hot shape: the fast obs path");
+  // hot shape: the launch's scalars, read once (keep_sgpr; QS_LAUNCH_VAL picks them)
+  [[maybe_unused]] const int trunc_at_h = kHotScal ? keep_sgpr(P.trunc_at) : 0, log_per_env_h = kHotScal ? keep_sgpr(P.log_per_env) : 0;
+  [[maybe_unused]] qs_episode_rec* const log_h = kHotScal ? keep_sgpr(P.log) : nullptr;
+  [[maybe_unused]] float* const hist_h = kHotScal ? keep_sgpr(P.hist) : nullptr;
+  [[maybe_unused]] const uint32_t k0_h = kHotScal ? keep_sgpr(P.k0) : 0u, k1_h = kHotScal ? keep_sgpr(P.k1) : 0u;
+  [[maybe_unused]] const T ctrl_dt_h = kHotScal ? keep_sgpr(P.ctrl_dt) : T(0), ctrl_hz_h = kHotScal ? keep_sgpr(P.ctrl_hz) : T(0);
+  [[maybe_unused]] const T dt_h = kHotScal ? keep_sgpr(P.dt) : T(0), hdt_h = kHotScal ? keep_sgpr(P.hdt) : T(0);
+  [[maybe_unused]] const T hdt2_h = kHotScal ? keep_sgpr(P.hdt2) : T(0);
   auto pend_read = [&](float4 (&v)[kPipeIt]) {
     const float4* const s4 = reinterpret_cast<const float4*>(stage);
 #pragma unroll
@@ -1095,7 +1161,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
 #pragma unroll
       for (int k = 0; k < A; ++k) cur_act[k] = act_in[k];
     } else {
-      U4 r = philox(U4{(uint32_t)total, genv, 0u, (uint32_t)((STREAM_ACT << 24) | d)}, P.k0, P.k1);
+      U4 r = philox(U4{(uint32_t)total, genv, 0u, (uint32_t)((STREAM_ACT << 24) | d)}, QS_LAUNCH_VAL(k0), QS_LAUNCH_VAL(k1));
       const uint32_t rr[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
       for (int k = 0; k < A; ++k) cur_act[k] = 2.0f * u01<float>(rr[k]) - 1.0f;
@@ -1109,6 +1175,11 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     if (pend_now) pend_read(pv);
     issue_fence();
   }
+  // hot shape: the wave's ballot of `dn`, and the first lanes' episode figures for the log
+  [[maybe_unused]] unsigned long long dn_wave = 0;
+  [[maybe_unused]] bool dn_h = false;
+  [[maybe_unused]] double ret_h = 0;
+  [[maybe_unused]] int len_h = 0;
   if (mode == MODE_STEP) {
     const float* act = cur_act;
     // ---------------- _preprocessAction (BaseRLAviary.py:188-239)
@@ -1126,7 +1197,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
         if (!qs_dev::kNoCompute && !kCarryRpy) quat_to_rpy(q, rpy);
         if constexpr (ACT == QS_ACT_ONE_D_PID) {
           T tp[3] = {pos[0], pos[1], pos[2] + T(0.1) * T(act[0])};
-          dsl_pid<T, kP>(P.ctrl_dt, P.ctrl_hz, pid, pos, q, vel, rpy, tp, T(0), z3, rpm);
+          dsl_pid<T, kP>(QS_LAUNCH_VAL(ctrl_dt), QS_LAUNCH_VAL(ctrl_hz), pid, pos, q, vel, rpy, tp, T(0), z3, rpm);
         } else if constexpr (ACT == QS_ACT_VEL) {
           T v0 = T(act[0]), v1 = T(act[1]), v2 = T(act[2]);
           T n = F::sqrt_(v0 * v0 + v1 * v1 + v2 * v2);
@@ -1134,14 +1205,14 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
           if (n != T(0)) { u0 = v0 / n; u1 = v1 / n; u2 = v2 / n; }
           T sp = T(cf2x::SPEED_LIMIT) * F::abs_(T(act[3]));
           T tv[3] = {sp * u0, sp * u1, sp * u2};
-          dsl_pid<T, kP>(P.ctrl_dt, P.ctrl_hz, pid, pos, q, vel, rpy, pos, rpy[2], tv, rpm);
+          dsl_pid<T, kP>(QS_LAUNCH_VAL(ctrl_dt), QS_LAUNCH_VAL(ctrl_hz), pid, pos, q, vel, rpy, pos, rpy[2], tv, rpm);
         } else {   // QS_ACT_PID: _calculateNextStep (BaseAviary.py:1108-1150)
           T dir[3] = {T(act[0]) - pos[0], T(act[1]) - pos[1], T(act[2]) - pos[2]};
           T dist = F::sqrt_(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]);
           T np_[3];
           if (dist <= T(1)) { np_[0] = T(act[0]); np_[1] = T(act[1]); np_[2] = T(act[2]); }
           else { for (int i = 0; i < 3; ++i) np_[i] = pos[i] + (dir[i] / dist) * T(1); }
-          dsl_pid<T, kP>(P.ctrl_dt, P.ctrl_hz, pid, pos, q, vel, rpy, np_, T(0), z3, rpm);
+          dsl_pid<T, kP>(QS_LAUNCH_VAL(ctrl_dt), QS_LAUNCH_VAL(ctrl_hz), pid, pos, q, vel, rpy, np_, T(0), z3, rpm);
         }
       }
     }
@@ -1159,9 +1230,9 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     if (valid) {
       // one vector store per lane for the A components (a wave writes whole
       // lines; per-component dword stores left 16-B-strided partial lines)
-      if (io.act_out) store_act<A>(io.act_out + (size_t)a * A, act);
+      if (kHotOuts ? true : io.act_out != nullptr) store_act<A>(io.act_out + (size_t)a * A, act);
       // action_buffer.append(action) (BaseRLAviary.py:187): ring slot total % H
-      store_act<A>(P.hist + ((size_t)wslot * N + a) * A, act);
+      store_act<A>(QS_LAUNCH_VAL(hist) + ((size_t)wslot * N + a) * A, act);
       if constexpr (kPid && !kFuse) {   // PID integrators are final: store now, drains under the substeps
 #pragma unroll
         for (int i = 0; i < 9; ++i) SA.st(QS_F_PID_INT_POS + i, pid[i]);
@@ -1180,7 +1251,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     // PYB: the four prop forces act at their links' COMs (assets/cf2x.urdf:42-79, cf2p.urdf:42-79)
     const T pbx = (((T(MD::PY[0]) * f[0]) + T(MD::PY[1]) * f[1]) + T(MD::PY[2]) * f[2]) + T(MD::PY[3]) * f[3];
     const T pby = (((-T(MD::PX[0]) * f[0]) + -T(MD::PX[1]) * f[1]) + -T(MD::PX[2]) * f[2]) + -T(MD::PX[3]) * f[3];
-    const T dt = P.dt;
+    const T dt = QS_LAUNCH_VAL(dt);
     // The exp-map update preserves |q| (cos²θ + sin²θ = 1), so in fp32 Bullet's
     // s = 2/|q|² (getMatrixFromQuaternion) is formed once per control step; it
     // moves by rounding only between substeps.
@@ -1487,7 +1558,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
         const T amax = T(0.25 * M_PI) / dt;
         if (ang2 > amax * amax) ang2 = amax * amax;
         T c, kk;
-        expmap_coeffs(ang2, P.hdt, P.hdt2, c, kk);   // cos(|ω|dt/2), sin(|ω|dt/2)/|ω|
+        expmap_coeffs(ang2, QS_LAUNCH_VAL(hdt), QS_LAUNCH_VAL(hdt2), c, kk);   // cos(|ω|dt/2), sin(|ω|dt/2)/|ω|
         const T e0 = ww0 * kk, e1 = ww1 * kk, e2 = ww2 * kk;
         const T x0 = q[0], x1 = q[1], x2 = q[2], x3 = q[3];
         T n0 = ((c * x0 + e0 * x3) + e1 * x2) - e2 * x1;
@@ -1547,7 +1618,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
         const T wn2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
         if (wn2 > T(1e-16)) {
           T c, k;
-          expmap_coeffs(wn2, P.hdt, P.hdt2, c, k);
+          expmap_coeffs(wn2, QS_LAUNCH_VAL(hdt), QS_LAUNCH_VAL(hdt2), c, k);
           const T p_ = w[0], q_ = w[1], r_ = w[2];
           const T x0 = q[0], x1 = q[1], x2 = q[2], x3 = q[3];
           q[0] = c * x0 + k * (r_ * x1 - q_ * x2 + p_ * x3);
@@ -1652,15 +1723,15 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     if (valid && d == 0) {
       T r = rsum / T(D);
       bool te = any != 0;
-      bool tr = step_counter >= P.trunc_at;   // step_counter / PYB_FREQ > EPISODE_LEN_SEC (MultiHoverAviary.py:267-268, step_trunc.h)
+      bool tr = step_counter >= QS_LAUNCH_VAL(trunc_at);   // step_counter / PYB_FREQ > EPISODE_LEN_SEC (MultiHoverAviary.py:267-268, step_trunc.h)
       if constexpr (kMarl) {
         r = marl_reward<T>(P.task, &s.cand[tid], &s.velw[tid], D);
         te = P.task == QS_TASK_MEETUP && meetup_met<T>(&s.cand[tid], D);
         tr = any != 0 || tr;   // (no termination-reason strings for these tasks)
       }
-      if (io.rew) io.rew[e] = r;
-      if (io.term) io.term[e] = te;
-      if (io.trunc) io.trunc[e] = tr;
+      if (kHotOuts ? true : io.rew != nullptr) io.rew[e] = r;
+      if (kHotOuts ? true : io.term != nullptr) io.term[e] = te;
+      if (kHotOuts ? true : io.trunc != nullptr) io.trunc[e] = tr;
       ret = ep_ret0 + (double)r;
       len = ep_len + 1;
       dn = te || tr;
@@ -1672,15 +1743,18 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     // each env appends to its own ring, slot = its logged count mod log_per_env —
     // no atomic (a returned global slot made the finishing waves wait ~µs for it
     // and for all their outstanding stores, and they set the launch's tail).
-    if (dn) {
+    if (kHotTail ? false : dn) {   // (hot shape: where an env of the wave has ended, below)
       qs_episode_rec rec;
       rec.ret = ret; rec.len = len; rec.env = (int32_t)genv; rec.seq = total;
       P.log[(size_t)e * P.log_per_env + (unsigned)log_n % (unsigned)P.log_per_env] = rec;
       log_n = log_n + 1;
     }
-    if (io.reasons && valid) io.reasons[a] = kMarl ? 0 : bits;
+    if (kHotOuts ? false : (io.reasons && valid)) io.reasons[a] = kMarl ? 0 : bits;
     step_counter += S;   // BaseAviary.py:382
-    if (wave_red) {   // the env's first lane holds dn: its bit of the wave's ballot
+    if constexpr (kHotTail) {   // done_env stays false; formed from the ballot where it is not zero, below
+      dn_wave = __ballot(dn);
+      dn_h = dn; ret_h = ret; len_h = len;
+    } else if (wave_red) {   // the env's first lane holds dn: its bit of the wave's ballot
       done_env = valid && ((__ballot(dn) >> (tid - d)) & 1ull) != 0;
     } else {
       __syncthreads();
@@ -1709,8 +1783,15 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     done_env = valid && masked;
   }
   // worker.step_env resets on done unless this is a single-env facade
+  if constexpr (kHotTail) {
+    do_reset = false;   // (where an env of the wave has ended: below)
+  } else if constexpr (kHotReset) {
+    do_reset = done_env;
+    any_reset = any_reset || do_reset;
+  } else {
   do_reset = done_env && !(mode == MODE_STEP && (P.flags & QS_FLAG_NO_AUTORESET));
   any_reset = any_reset || do_reset;
+  }
 
   // ---------------- obs writer (BaseRLAviary._computeObs + Spiral extras)
   auto write_obs_row = [&](float* o, int sc) {
@@ -1761,11 +1842,31 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   };
 
   QS_STAMP(4);
-  if (valid && done_env && mode == MODE_STEP && io.tobs) write_obs_row(io.tobs + (size_t)a * O, obs_sc);
+  if (kHotOuts ? false : (valid && done_env && mode == MODE_STEP && io.tobs)) write_obs_row(io.tobs + (size_t)a * O, obs_sc);
 
   // ---------------- auto-reset (worker.step_env → env.reset)
   bool some_reset;   // workgroup-uniform: some env of this wave resets
-  if (wave_red) {
+  if constexpr (kHotTail) {
+    // hot shape: everything an ended episode brings hangs on this one wave-uniform
+    // value; the usual step, in which no env of the wave ends, goes on to its obs rows
+    some_reset = dn_wave != 0;
+    if (some_reset) {
+      if (dn_h) {   // the episode log, as above
+        qs_episode_rec rec;
+        rec.ret = ret_h; rec.len = len_h; rec.env = (int32_t)genv; rec.seq = total;
+        QS_LAUNCH_VAL(log)[(size_t)e * QS_LAUNCH_VAL(log_per_env) + (unsigned)log_n % (unsigned)QS_LAUNCH_VAL(log_per_env)] = rec;
+        log_n = log_n + 1;
+      }
+      done_env = ((dn_wave >> (tid - d)) & 1ull) != 0;
+      if constexpr (kHotReset) do_reset = done_env;
+      else do_reset = done_env && !(P.flags & QS_FLAG_NO_AUTORESET);
+      any_reset = any_reset || do_reset;
+      if constexpr (!kHotOuts) {
+        if (done_env && io.tobs) write_obs_row(io.tobs + (size_t)a * O, obs_sc);
+      }
+      if constexpr (!kHotReset) some_reset = __ballot(do_reset) != 0;
+    }
+  } else if (wave_red) {
     some_reset = __ballot(do_reset) != 0;
   } else {
     s.any = 0;
@@ -1775,11 +1876,15 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     some_reset = s.any != 0;
   }
   if (some_reset) {
-    if (d == 0 && lenv < P.EPB) s.need[lenv] = do_reset ? 1 : 0;
+    if (kHotReset ? false : (d == 0 && lenv < P.EPB)) s.need[lenv] = do_reset ? 1 : 0;
     if (mode != MODE_RESET_ALL && do_reset) episode += 1;
     T init[3] = {orig[0], orig[1], orig[2]};
     if constexpr (kHover) {
-      if (P.reject_free) {   // workgroup-uniform: no pair test, no barriers
+      if (kHotReset ? true : P.reject_free != 0) {   // workgroup-uniform: no pair test, no barriers
+        if constexpr (kHotScal) {
+          if (do_reset && !qs_dev::kNoResetDraw)
+            reset_candidate(k0_h, k1_h, orig, d, 0u, genv, (uint32_t)episode, init[0], init[1], init[2]);
+        } else
         if (do_reset && !qs_dev::kNoResetDraw)
           reset_candidate(P, orig, d, 0u, genv, (uint32_t)episode, init[0], init[1], init[2]);
       } else {
@@ -1879,13 +1984,13 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   QS_STAMP(5);
   // ---------------- obs output
   if constexpr (kPipe) pend = nullptr;   // (the span of the step before went out above)
-  if (io.obs) {
+  if (kHotOuts ? true : io.obs != nullptr) {
     if (kPipe && pipe) {
       // fast path: the rows stay in the stage; the next step (or the code after
       // the loop) copies the span out
       if (valid) write_obs_row(stage + tid * O, obs_sc);
       issue_fence();
-      pend = io.obs + (size_t)blockIdx.x * P.EPB * D * O;
+      pend = io.obs + (size_t)blockIdx.x * QS_EPB * D * O;
     } else if (mode == MODE_RESET_MASK) {
       if (valid && do_reset) write_obs_row(io.obs + (size_t)a * O, obs_sc);
     } else {
@@ -1970,8 +2075,8 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   }
   __syncthreads();
   {
-    const int nrec = min(P.EPB, P.E - (int)blockIdx.x * P.EPB) * kEnvRec;
-    int32_t* const g = P.env + (size_t)blockIdx.x * P.EPB * kEnvRec;
+    const int nrec = kHotShape ? kBlock / kHotD * kEnvRec : min(P.EPB, P.E - (int)blockIdx.x * P.EPB) * kEnvRec;
+    int32_t* const g = P.env + (size_t)blockIdx.x * QS_EPB * kEnvRec;
     for (int i = tid; i < nrec; i += kBlock) __builtin_nontemporal_store(s.rec[i], g + i);
   }
   if (!valid) return;
@@ -2000,6 +2105,8 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   }
 }
 
+#undef QS_LAUNCH_VAL
+#undef QS_EPB
 
 // ------------------------------------------------- deferred reset search
 // MultiHoverAviary.reset's rejection loop (MH:83-102) for the envs the step

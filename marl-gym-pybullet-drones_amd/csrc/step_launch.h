@@ -14,4 +14,10 @@ namespace qs {
 template <class T, int TASK, int FUSE = 0>
 bool launch_task(int act, int grid, size_t lds, hipStream_t st, const KernelParams<T, FUSE>& P, int cf, int pf, int ph,
                  const void** fn = nullptr, bool select_only = false);
+// The shape-specialised multi-step instance (step_kernel HOT = 1; step_mh_hot.hip)
+// for a launch qs::hot_shape_ok accepts: MultiHover, ONE_D_PID, 30 Hz, no extra
+// forces, D = 8; `phys` picks DYN or PYB.
+template <class T>
+void launch_hot(int phys, int grid, size_t lds, hipStream_t st, const ParamsMany<T>& P, const void** fn = nullptr,
+                bool select_only = false);
 }  // namespace qs

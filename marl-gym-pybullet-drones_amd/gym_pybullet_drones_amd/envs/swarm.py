@@ -261,6 +261,14 @@ class QuadSwarm:
             L.check(self.lib.qs_step_seq(self._h, n, ptrs, arr, self._stream()), "qs_step_seq")
         return [res for _, res in recs]
 
+    def launch_counts(self):
+        """(general, hot): the multi-step launches made so far on the general kernel
+        instances and on the shape-specialised one (qs_launch_counts; QS_HOT_SHAPE=0
+        at construction keeps every launch on the general ones)."""
+        out = (ctypes.c_int64 * 2)()
+        L.check(self.lib.qs_launch_counts(self._h, out), "qs_launch_counts")
+        return int(out[0]), int(out[1])
+
     # ------------------------------------------------------------ state I/O
     def _state_buf(self, block):
         kw = dict(device=self.device)
