@@ -277,6 +277,64 @@ int qs_step_many(qs_handle* h, int n, const qs_step_out* outs, void* stream);
 int qs_step_seq(qs_handle* h, int n, const float* const* actions,
                 const qs_step_out* outs, void* stream);
 
+/* Branch rollouts: C candidate action sequences of n steps each, all from the
+ * handle's current state, in one launch that leaves the handle as it was (what a
+ * sampling planner does once per control tick).  The launch runs C · E virtual
+ * envs, virtual env c · E + e starting from the state of env e, so it fills
+ * wavefronts whatever E is.  (New entry points of ABI 4, like qs_step_seq.)
+ *
+ * actions: a host array of n device pointers, read during the call, each
+ * [C][E][D][A] float32.  outs: n sets of step outputs or NULL, every buffer
+ * sized for C · E envs (obs [C][E][D][O], reward [C][E], ...).  score: the
+ * per-candidate summary below, or NULL.
+ *
+ *  - Equivalence.  For every candidate c the per-step outputs equal, bit for
+ *    bit, what qs_step_seq(h', n, actions[.][c], outs', stream) writes on a
+ *    handle h' whose four state blocks equal h's at the time of the call,
+ *    auto-resets inside the candidate included: the reset draw is keyed on the
+ *    source env's global id and episode counter, so it is the same in every
+ *    candidate.  QS_FLAG_NO_AUTORESET handles are included.
+ *  - No mutation.  h is not advanced: agent state, env record, history ring,
+ *    episode return, episode log (records and total), reset-error flag and
+ *    qs_launch_counts are unchanged byte for byte after the call.
+ *  - Optional outputs.  Every pointer in outs[j] may be NULL, outs may be NULL,
+ *    and score or either of its members may be NULL; a call with nothing to
+ *    write is QS_E_INVALID.
+ *  - Alignment.  Actions need 4-byte alignment only, and steps may share action
+ *    buffers.  No output may overlap another output or any action buffer
+ *    (QS_E_INVALID).  Nothing is cut into several launches: state cannot be
+ *    carried between launches.
+ *  - Depth.  1 <= n <= qs_score_depth(h): 32, lowered only where the steps'
+ *    action rows (256 · A bytes per step and workgroup) plus the kernel's other
+ *    LDS would pass the 64 KB a workgroup of the action-sequence launches may
+ *    take.  It depends neither on C nor on QS_MAX_FUSED_STEPS.  Longer horizons
+ *    are refused, not approximated.
+ *  - Handles that cannot score: qs_score_depth returns 0 and qs_score
+ *    QS_E_INVALID with a message for handles that run the deferred reset search
+ *    after each step (MultiHover layouts whose reset draws can be rejected) and
+ *    for the Flock / Meetup / LeaderFollower tasks (their multi-step kernels
+ *    round the env reward 1 ulp apart from the single step's).
+ *  - Other refusals.  C < 1, n out of range or a NULL among actions[]:
+ *    QS_E_INVALID; C · E · D too large for the 32-bit offsets of a requested
+ *    output: QS_E_INVALID; a call before qs_reset: QS_E_STATE.
+ *  - Capture.  Like every other call on the handle it ends the kernel node a
+ *    captured qs_step was growing; the call itself may be captured. */
+typedef struct qs_score_out {
+  void* ret;           /* [C][E] double: sum, in step order and in double, of
+                          the (real) rewards of steps 0..jd, jd = the candidate's
+                          first step with terminated|truncated for that env, or
+                          n-1 if none                                          */
+  int32_t* first_done; /* [C][E]: jd, or n if the env was never done in the
+                          candidate                                            */
+} qs_score_out;
+
+/* Largest n one qs_score call takes on this handle (0: the handle cannot
+ * score).  Host only. */
+int qs_score_depth(const qs_handle* h);
+
+int qs_score(qs_handle* h, int n, int C, const float* const* actions,
+             const qs_step_out* outs, const qs_score_out* score, void* stream);
+
 /* Multi-step launches this handle has made so far (host, no device work):
  * out[0] on the general multi-step kernel instances, out[1] on the
  * shape-specialised one.  The specialised instance serves synthetic-policy

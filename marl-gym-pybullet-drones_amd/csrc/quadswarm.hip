@@ -3,8 +3,9 @@
 // csrc/step_kernel.h; the kernels are instantiated per task family in
 // step_mh.hip / step_spiral.hip / step_marl.hip (single step), their
 // *_fused.hip twins (several control steps per launch), step_mh_seq.hip /
-// step_spiral_seq.hip (the same over caller-supplied actions) and step_mh_hot.hip
-// (MultiHover's shape-specialised multi-step instances).
+// step_spiral_seq.hip (the same over caller-supplied actions), step_mh_score.hip /
+// step_spiral_score.hip (branch rollouts that leave the handle alone) and
+// step_mh_hot.hip (MultiHover's shape-specialised multi-step instances).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -18,6 +19,7 @@
 #include "quadswarm.h"
 #include "step_launch.h"
 #include "step_fuse.h"
+#include "step_score.h"
 #include "step_trunc.h"
 
 static_assert(qs::kFuseMax == qs::kMaxFuse, "step_fuse.h and step_kernel.h disagree on the fusion depth");
@@ -29,6 +31,10 @@ static_assert(qs::kHotTask == QS_TASK_MULTIHOVER && qs::kHotAct == QS_ACT_ONE_D_
               "step_fuse.h restates quadswarm.h's values for the hot shape");
 static_assert(qs::kHotDrones == qs::kHotD && qs::kHotEnvs == qs::kBlock / qs::kHotD && qs::kFuseOuts == 7,
               "step_fuse.h and step_kernel.h disagree on the hot shape");
+
+static_assert(qs::kScoreMaxSteps == qs::kMaxFuse && qs::kScoreStepBytes == qs::kSeqStepBytes &&
+                  qs::kScoreStepOuts == qs::kFuseOuts,
+              "step_score.h disagrees with step_kernel.h / step_fuse.h on a launch's steps, action rows or outputs");
 
 namespace qs {
 // Calibration kernel: dword per lane, grid-stride (MI355X_MICROARCH §HBM).
@@ -283,7 +289,8 @@ struct LaunchInfo {
 // multi-step instance over P.io[0 .. P.nsteps-1] (MODE_STEP, no trainer actions,
 // no deferred reset queue: the callers see to that); FUSE = 2: the same over the
 // actions P.act[0 .. P.nsteps-1], whose rows take LDS of their own (the caller
-// has capped P.nsteps by seq_depth).  select_only: no launch.
+// has capped P.nsteps by seq_depth); FUSE = 3: the FUSE = 2 launch over P.E
+// virtual envs (qs_score, P.nsteps within score_depth).  select_only: no launch.
 template <class T, int FUSE>
 static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t st, LaunchInfo* info, bool select_only,
                          int* kind = nullptr) {
@@ -323,7 +330,7 @@ static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t
       }
     }
   }
-  if constexpr (FUSE == 2) {
+  if constexpr (FUSE == 2 || FUSE == 3) {
     lds = seq_lds_base(h, lds) + (size_t)P.nsteps * qs::kSeqStepBytes * (size_t)h->dims.act_dim;
     if (lds + kLdsStatic > kLdsBytes) return fail(QS_E_INVALID, "launch: the steps' action rows do not fit in LDS");
   }
@@ -335,7 +342,7 @@ static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t
   else if (s.task == QS_TASK_SPIRAL)
     ok = qs::launch_task<T, QS_TASK_SPIRAL, FUSE>(s.act_type, grid, lds, st, P, s.ctrl_freq, s.pyb_freq, s.physics, &fn,
                                                   select_only);
-  else if constexpr (FUSE == 2)
+  else if constexpr (FUSE == 2 || FUSE == 3)
     return fail(QS_E_INVALID, "launch: no action-sequence instances of the Flock / Meetup / LeaderFollower family");
   else
     ok = qs::launch_task<T, qs::kTaskMarl, FUSE>(s.act_type, grid, lds, st, P, s.ctrl_freq, s.pyb_freq, s.physics, &fn,
@@ -605,6 +612,79 @@ template <class T> static int step_seq_impl(qs_handle* h, int n, const float* co
   return QS_OK;
 }
 
+// ---------------------------------------------------------------- branch rollouts
+// Why a handle cannot score (nullptr: it can).
+static const char* score_refusal(const qs_handle* h) {
+  if (h->rq) return "this layout's reset draws can be rejected and the deferred search launch runs after each step";
+  if (h->spec.task != QS_TASK_MULTIHOVER && h->spec.task != QS_TASK_SPIRAL)
+    return "the multi-step kernels of the Flock / Meetup / LeaderFollower family round the env reward 1 ulp apart "
+           "from the single step's";
+  return nullptr;
+}
+// Steps of one qs_score launch (step_score.h).  The LDS figures are those of a
+// launch whose workgroups need not share a CU (lds_plan at residency 1: the
+// largest obs stage any launch of the handle gets), so the depth depends
+// neither on C nor on QS_MAX_FUSED_STEPS.
+static int score_depth(const qs_handle* h) {
+  if (score_refusal(h)) return 0;
+  int stage_rows = 0;
+  size_t plan = 0;
+  if (lds_plan(h->dims, envs_per_wave(h), 1, &stage_rows, &plan) != QS_OK) return 0;
+  const size_t hist = (size_t)h->dims.hist_len * qs::kBlock * h->dims.act_dim * sizeof(float);
+  const size_t image = fixed_ctrl_freq(h->spec) ? 0 : hist;
+  return qs::score_depth(kSeqLdsMax, kLdsStatic + kLdsGrain, image, plan - hist, h->dims.act_dim);
+}
+
+template <class T> static int score_impl(qs_handle* h, int n, int C, const float* const* actions, const qs_step_out* outs,
+                                         const qs_score_out* score, hipStream_t st) {
+  const qs_dims& d = h->dims;
+  uint64_t bytes[qs::kScoreOuts], act_bytes = 0;
+  const qs::ScoreShape shape{C, d.num_envs, d.num_drones, d.obs_dim, d.act_dim, d.precision};
+  if (!qs::score_sizes(shape, bytes, &act_bytes) || !qs::score_fits(act_bytes))
+    return fail(QS_E_INVALID, "qs_score: C * num_envs * num_drones is too large for one launch (32-bit offsets)");
+  qs::ScoreRanges ranges;
+  bool any_out = false, room = true;
+  const char* const names[qs::kScoreOuts] = {"obs", "reward", "terminated", "truncated", "terminal_obs", "reasons",
+                                             "actions_out", "ret", "first_done"};
+  auto add_out = [&](const void* p, int i) -> bool {   // false: too large to address
+    if (!p) return true;
+    any_out = true;
+    if (!qs::score_fits(bytes[i])) return false;
+    room = ranges.add(p, bytes[i], false) && room;
+    return true;
+  };
+  for (int j = 0; j < n; ++j) {
+    room = ranges.add(actions[j], act_bytes, true) && room;
+    if (!outs) continue;
+    const qs::FuseOuts fo = to_outs(outs[j]);
+    for (int i = 0; i < qs::kFuseOuts; ++i)
+      if (!add_out(fo.p[i], i))
+        return fail(QS_E_INVALID, std::string("qs_score: ") + names[i] + " of C * num_envs envs is too large (32-bit offsets)");
+  }
+  if (score) {
+    if (!add_out(score->ret, 7) || !add_out(score->first_done, 8))
+      return fail(QS_E_INVALID, "qs_score: C * num_envs is too large (32-bit offsets)");
+  }
+  if (!any_out) return fail(QS_E_INVALID, "qs_score: nothing to write (no output in outs[] and neither ret nor first_done)");
+  if (!room || ranges.overlap())
+    return fail(QS_E_INVALID, "qs_score: an output overlaps another output or an action buffer");
+  qs::ParamsScore<T> P;
+  std::memset(&P, 0, sizeof(P));
+  fill_params(h, P);
+  P.mode = qs::MODE_STEP;
+  P.E_src = d.num_envs;
+  P.E = C * d.num_envs;          // the virtual envs; P.N stays the handle's agent count
+  P.reset_queue = nullptr;       // (score_refusal: none)
+  P.store_state = 0;             // nothing is stored to the handle, ever
+  P.nsteps = n;
+  for (int j = 0; j < n; ++j) {
+    if (outs) P.io[j] = to_io<T>(outs[j]);
+    P.act[j] = actions[j];
+  }
+  if (score) { P.ret = (double*)score->ret; P.first_done = score->first_done; }
+  return launch_kernel<T, 3>(h, P, st, nullptr, false);
+}
+
 extern "C" {
 
 const char* qs_last_error(void) { return g_err.c_str(); }
@@ -870,6 +950,28 @@ int qs_step_seq(qs_handle* h, int n, const float* const* actions, const qs_step_
   }
   if (h->dims.precision == 8) return step_seq_impl<double>(h, n, actions, outs, st);
   return step_seq_impl<float>(h, n, actions, outs, st);
+}
+
+int qs_score_depth(const qs_handle* h) { return h ? score_depth(h) : 0; }
+
+int qs_score(qs_handle* h, int n, int C, const float* const* actions, const qs_step_out* outs, const qs_score_out* score,
+             void* stream) {
+  if (!h) return fail(QS_E_INVALID, "qs_score: null handle");
+  if (const char* why = score_refusal(h)) return fail(QS_E_INVALID, std::string("qs_score: this handle cannot score: ") + why);
+  const int depth = score_depth(h);
+  if (depth < 1) return fail(QS_E_INVALID, "qs_score: this handle cannot score: no step's action rows fit in LDS");
+  if (C < 1) return fail(QS_E_INVALID, "qs_score: C must be >= 1");
+  if (n < 1 || n > depth)
+    return fail(QS_E_INVALID, "qs_score: n = " + std::to_string(n) + " is outside 1 .. qs_score_depth = " +
+                                  std::to_string(depth) + " (longer horizons are not cut into several launches)");
+  if (!actions) return fail(QS_E_INVALID, "qs_score: actions is null");
+  for (int j = 0; j < n; ++j)
+    if (!actions[j]) return fail(QS_E_INVALID, "qs_score: actions[" + std::to_string(j) + "] is null");
+  if (!h->reset_done) return fail(QS_E_STATE, "qs_score: call qs_reset first");
+  h->fuse.forget();
+  hipStream_t st = (hipStream_t)stream;
+  if (h->dims.precision == 8) return score_impl<double>(h, n, C, actions, outs, score, st);
+  return score_impl<float>(h, n, C, actions, outs, score, st);
 }
 
 // qs_state_io's view of the per-env records: counters as [QS_ENV_FIELDS][E]

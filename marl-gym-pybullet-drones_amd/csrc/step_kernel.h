@@ -310,8 +310,20 @@ template <class T> struct ParamsMany : Params<T> {
 template <class T> struct ParamsSeq : ParamsMany<T> {
   const float* act[kMaxFuse];
 };
+// Arguments of the branch-rollout instances (step_kernel FUSE = 3, qs_score): E
+// counts the launch's virtual envs, C candidates × E_src envs of the handle
+// (virtual env v = c · E_src + e), and N stays the handle's agent count: what
+// reads the handle indexes by v mod E_src, the actions and every output by v.
+// Once more a type of its own: Params, ParamsMany and ParamsSeq keep their size.
+template <class T> struct ParamsScore : ParamsSeq<T> {
+  int E_src;
+  int store_state;       // always 0: nothing is stored to the handle (see the end of step_kernel for why it exists)
+  double* ret;           // [E] or NULL: the candidate's return up to its first done
+  int32_t* first_done;   // [E] or NULL: that step, nsteps if none
+};
 template <class T, int FUSE>
-using KernelParams = std::conditional_t<FUSE == 2, ParamsSeq<T>, std::conditional_t<FUSE != 0, ParamsMany<T>, Params<T>>>;
+using KernelParams = std::conditional_t<FUSE == 3, ParamsScore<T>,
+    std::conditional_t<FUSE == 2, ParamsSeq<T>, std::conditional_t<FUSE != 0, ParamsMany<T>, Params<T>>>>;
 
 // ---------------------------------------------------- conversions (external)
 // pybullet getMatrixFromQuaternion = btMatrix3x3::setRotation (s = 2/|q|²).
@@ -793,6 +805,8 @@ template <class T> __device__ __forceinline__ int launch_steps(const Params<T>&)
 template <class T> __device__ __forceinline__ int launch_steps(const ParamsMany<T>& P) { return P.nsteps; }
 template <class T> __device__ __forceinline__ bool launch_obs_pipe(const Params<T>&) { return false; }
 template <class T> __device__ __forceinline__ bool launch_obs_pipe(const ParamsMany<T>& P) { return P.obs_pipe != 0; }
+template <class T> __device__ __forceinline__ int launch_src_envs(const Params<T>& P) { return P.E; }
+template <class T> __device__ __forceinline__ int launch_src_envs(const ParamsScore<T>& P) { return P.E_src; }
 
 // ---------------------------------------------------------------- the step
 // TASK (qs_task) and ACT (qs_action_type) are compile-time: each launch runs
@@ -827,6 +841,17 @@ template <class T> __device__ __forceinline__ bool launch_obs_pipe(const ParamsM
 // aligned buffer will do), and a step takes its row from there where FUSE = 1
 // draws: the loop still issues no global load.  Everything else is the shared
 // body.
+// FUSE = 3: the FUSE = 2 loop as a branch rollout that leaves the handle alone
+// (qs_score, ParamsScore).  The grid runs C · E_src virtual envs; virtual env v
+// loads the state of the handle's env v mod E_src and steps it through
+// candidate v / E_src's actions.  No store to the handle runs: the history slot,
+// the episode log, the reset error flag and the env record are compiled out, the
+// state stores after the loop sit behind a launch value that is always 0 (as a
+// compile-time test it moved the substeps' fp32 rounding, see there); the
+// per-step outputs are those of FUSE = 2, bit for bit, and the
+// env's first lane also sums the rewards up to the first done step.  Each of
+// its statements is chosen by a compile-time test, so the other instances
+// compile to the code they had.
 // HOT = 1 (FUSE = 1, MultiHover, compile-time control frequency, AUXM 0 only):
 // the launch shape qs::hot_shape_ok (step_fuse.h) accepts, with everything that
 // predicate fixes for the launch folded in ("hot shape"): D = 8
@@ -895,7 +920,16 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   const int e = blockIdx.x * QS_EPB + lenv;
   const bool valid = kHotShape ? true : ((lenv < P.EPB) && (e < P.E));
   const int a = e * D + d;
-  const uint32_t genv = (uint32_t)(P.env_offset + e);
+  // FUSE = 3 (qs_score): e is a virtual env, candidate e / E_src of the handle's
+  // env e mod E_src.  It loads that env's state, history and record (e_h, a_h:
+  // the handle's env and agent), draws its resets under that env's global id, so
+  // every candidate sees the same draw, and stores nothing to the handle: the
+  // history slot, the episode log, the error flag and the env record are compiled
+  // out below, the final state stores skipped (ParamsScore::store_state, always
+  // 0).  Actions and outputs index by e and a as ever.
+  constexpr bool kScore = FUSE == 3;
+  const int e_h = kScore ? e % launch_src_envs(P) : e, a_h = kScore ? e_h * D + d : a;
+  const uint32_t genv = (uint32_t)(P.env_offset + e_h);
   // kBlock == 64 is one wave: an env of 2, 4, 8 or 16 drones lies inside one
   // 16-lane DPP row, and the per-env reduction and flags need no LDS.  Multi-step
   // instances only: with the run-time choice between the two paths in it, the
@@ -906,7 +940,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   SoA<T> SA;
   SA.rsrc = __builtin_amdgcn_make_buffer_rsrc(P.st, 0, (int)((unsigned)QS_AGENT_FIELDS * (unsigned)N * sizeof(T)), 0x00020000);
   SA.fstride = (unsigned)N * (unsigned)sizeof(T);
-  SA.voff = (unsigned)a * (unsigned)sizeof(T);
+  SA.voff = (unsigned)a_h * (unsigned)sizeof(T);
   QS_STAMP(0);
 
   // ---------------- loads
@@ -921,12 +955,12 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, (int)bytes, 0x00020000);
   };
   SA.voff = valid ? SA.voff : kOOB;
-  const unsigned E = (unsigned)P.E;
+  const unsigned E = (unsigned)launch_src_envs(P);   // the handle's envs
   // env counters first: the synthetic action draw needs only `total`
   typedef unsigned v2u_t __attribute__((ext_vector_type(2)));
   static_assert(QS_E_STEP_COUNTER == 0 && QS_E_EPISODE == 1 && QS_E_TOTAL_STEPS == 2 && QS_E_EP_LEN == 3, "record");
   const __amdgpu_buffer_rsrc_t env_r = rsrc(P.env, (unsigned)kEnvRec * E * 4u);
-  const unsigned ev = valid ? (unsigned)e * kEnvRec * 4u : kOOB;
+  const unsigned ev = valid ? (unsigned)e_h * kEnvRec * 4u : kOOB;
   const v2u_t c01 = __builtin_amdgcn_raw_buffer_load_b64(env_r, (int)ev, 0, 0);
   const v2u_t c23 = __builtin_amdgcn_raw_buffer_load_b64(env_r, (int)ev, 8, 0);
   int32_t step_counter = (int32_t)c01.x, episode = (int32_t)c01.y;
@@ -938,7 +972,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   // chunks it has rejected so far, so a queued env's search starts past them; a
   // null buffer reads 0 (num_records 0)
   const int32_t pre0 = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(
-      rsrc(P.reset_pre, P.reset_pre ? E * 4u : 0u), valid ? (int)(e * 4u) : (int)kOOB, 0, 0);
+      rsrc(P.reset_pre, P.reset_pre ? E * 4u : 0u), valid ? (int)(e_h * 4u) : (int)kOOB, 0, 0);
   issue_fence();
   T pos[3], q[4], vel[3], w[3], lrpm[4], pid[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tgt[3] = {0, 0, 0};
 #pragma unroll
@@ -972,7 +1006,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     for (int k = 0; k < A; ++k) act_in[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)(v + 4u * k), 0, 0));
   }
   const uint8_t mask_v = __builtin_amdgcn_raw_buffer_load_b8(
-      rsrc(P.reset_mask, P.reset_mask ? E : 0u), valid ? e : (int)kOOB, 0, 0);
+      rsrc(P.reset_mask, P.reset_mask ? E : 0u), valid ? e_h : (int)kOOB, 0, 0);
   const bool masked = P.reset_mask == nullptr || mask_v != 0;
   T orig[3];   // every search group needs it, also those past the last env (reset phase 2)
 #pragma unroll
@@ -989,7 +1023,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   extern __shared__ float4 dyn_lds4[];   // float4: 16-B aligned staging for the obs stores
   // FUSE = 2: the launch's action rows come first, nsteps · A · kBlock floats
   // (a multiple of 256 bytes: the stage keeps its alignment)
-  constexpr bool kSeq = FUSE == 2;
+  constexpr bool kSeq = FUSE == 2 || FUSE == 3;
   float* const dyn_lds = reinterpret_cast<float*>(dyn_lds4);
   float* const act_lds = dyn_lds;
   float* const hist_pref = kSeq ? dyn_lds + (size_t)launch_steps(P) * kBlock * A : dyn_lds;
@@ -998,7 +1032,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   float hreg[HR][A];
   if constexpr (CF != 0) {
     const __amdgpu_buffer_rsrc_t hr = rsrc(P.hist, (unsigned)HR * (unsigned)N * A * 4u);
-    const unsigned hv = valid ? (unsigned)a * A * 4u : kOOB;
+    const unsigned hv = valid ? (unsigned)a_h * A * 4u : kOOB;
 #pragma unroll
     for (int sl = 0; sl < HR; ++sl) {
       const int so = (int)((unsigned)sl * (unsigned)N * A * 4u);
@@ -1010,7 +1044,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
         hreg[sl][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(hr, (int)(hv + 4u * k), so, 0));
     }
   } else {
-    const int a_src = valid ? a : blockIdx.x * P.EPB * D;   // idle lanes read a valid row
+    const int a_src = valid ? a_h : (kScore ? (int)((blockIdx.x * P.EPB) % launch_src_envs(P)) * D : blockIdx.x * P.EPB * D);   // idle lanes read a valid row
     for (int sl = 0; sl < H; ++sl) {
       const float* src = P.hist + ((size_t)sl * N + a_src) * A;
       if constexpr (A == 1) {
@@ -1063,6 +1097,10 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   int obs_sc = step_counter;   // step_counter seen by _computeObs (before BaseAviary.py:382)
   bool do_reset = false;
   bool any_reset = false;      // FUSE: some step of this launch reset the env (its target is stored at the end)
+  // FUSE = 3 (an env's first lane): the rewards of steps 0 .. first done, summed in
+  // step order in double, and that step (−1: not done yet)
+  [[maybe_unused]] double score_ret = 0;
+  [[maybe_unused]] int score_fd = -1;
 
   float cur_act[A];            // this step's action (newest history entry)
 #pragma unroll
@@ -1232,7 +1270,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
       // lines; per-component dword stores left 16-B-strided partial lines)
       if (kHotOuts ? true : io.act_out != nullptr) store_act<A>(io.act_out + (size_t)a * A, act);
       // action_buffer.append(action) (BaseRLAviary.py:187): ring slot total % H
-      store_act<A>(QS_LAUNCH_VAL(hist) + ((size_t)wslot * N + a) * A, act);
+      if constexpr (!kScore) store_act<A>(QS_LAUNCH_VAL(hist) + ((size_t)wslot * N + a) * A, act);
       if constexpr (kPid && !kFuse) {   // PID integrators are final: store now, drains under the substeps
 #pragma unroll
         for (int i = 0; i < 9; ++i) SA.st(QS_F_PID_INT_POS + i, pid[i]);
@@ -1738,16 +1776,24 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
       ep_ret_out = dn ? 0.0 : ret;
       ep_len_out = dn ? 0 : len;
       if (!wave_red) s.done[lenv] = dn;
+      if constexpr (kScore) {   // the candidate's return, up to and including its first done step
+        if (score_fd < 0) {
+          score_ret += (double)r;
+          if (dn) score_fd = ks;
+        }
+      }
     }
     // Episode log (VecRecordEpisodeStatistics, record_episode_statistics.py:155-166):
     // each env appends to its own ring, slot = its logged count mod log_per_env —
     // no atomic (a returned global slot made the finishing waves wait ~µs for it
     // and for all their outstanding stores, and they set the launch's tail).
+    if constexpr (!kScore) {
     if (kHotTail ? false : dn) {   // (hot shape: where an env of the wave has ended, below)
       qs_episode_rec rec;
       rec.ret = ret; rec.len = len; rec.env = (int32_t)genv; rec.seq = total;
       P.log[(size_t)e * P.log_per_env + (unsigned)log_n % (unsigned)P.log_per_env] = rec;
       log_n = log_n + 1;
+    }
     }
     if (kHotOuts ? false : (io.reasons && valid)) io.reasons[a] = kMarl ? 0 : bits;
     step_counter += S;   // BaseAviary.py:382
@@ -1901,7 +1947,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
         if (d == 0 && do_reset && s.reject[lenv] == 0) s.need[lenv] = 0;
         if (tid == 0) s.qcount = 0;
         __syncthreads();
-        if (P.reset_queue) {
+        if (kScore ? false : P.reset_queue != nullptr) {   // (qs_score refuses the handles that have a queue)
           // deferred: reset_search_kernel (next launch, same stream) finds the first
           // accepted try and rewrites the env's position, target and obs; try 0
           // stands in until then.  One returning atomic per
@@ -1930,7 +1976,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
         // (= sequential order).
         for (int k = 0; k < P.EPB; ++k) {
           if (!s.need[k]) continue;   // block-uniform (LDS)
-          const int ek = blockIdx.x * P.EPB + k;
+          const int ek = kScore ? (int)((blockIdx.x * P.EPB + k) % launch_src_envs(P)) : blockIdx.x * P.EPB + k;
           const uint32_t genv_k = (uint32_t)(P.env_offset + ek);
           // episode number of env k lives in its drone-0 thread; broadcast via LDS
           __syncthreads();
@@ -1949,7 +1995,10 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
             if (s.win_group < (1 << 30) || base + P.EPB >= kMaxResetTries) {
               if (tid == 0) {
                 if (s.win_group < (1 << 30)) s.win_try[k] = base + (uint32_t)s.win_group;
-                else { s.win_try[k] = 0; atomicExch(P.err, 1); }
+                else {
+                  s.win_try[k] = 0;
+                  if constexpr (!kScore) atomicExch(P.err, 1);
+                }
               }
               __syncthreads();
               break;
@@ -2062,7 +2111,14 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
       pend_store(pv, pend);
     }
   }
+  if constexpr (kScore) {   // the candidate's score, by the env's first lane
+    if (valid && d == 0) {
+      if (P.ret) P.ret[e] = score_ret;
+      if (P.first_done) P.first_done[e] = score_fd < 0 ? launch_steps(P) : score_fd;
+    }
+  }
   // ---------------- per-env records: staged in LDS, stored as one span
+  if constexpr (!kScore) {
   if (valid && d == 0) {
     int32_t* r = &s.rec[lenv * kEnvRec];
     const unsigned long long rb = __builtin_bit_cast(unsigned long long, ep_ret_out);
@@ -2079,9 +2135,19 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     int32_t* const g = P.env + (size_t)blockIdx.x * QS_EPB * kEnvRec;
     for (int i = tid; i < nrec; i += kBlock) __builtin_nontemporal_store(s.rec[i], g + i);
   }
+  }
   if (!valid) return;
 
   if constexpr (kFuse) {   // the state after the last step, once
+    // FUSE = 3 stores none: every qs_score launch passes store_state = 0 and leaves
+    // here.  The test is a launch value and not a compile-time one because with the
+    // stores below compiled out the backend paired the fp32 substeps' products
+    // into fmas differently (Spiral VEL and CF2P RPM came out 1 ulp off the
+    // FUSE = 2 instances in obs; the same count of every fp instruction either way,
+    // DESIGN.md §4a), while the history-slot, log and env-record stores could go.
+    if constexpr (kScore) {
+      if (P.store_state == 0) return;
+    }
     store_kin();
     if constexpr (kPid) {
 #pragma unroll

@@ -1,0 +1,6 @@
+// step_mh_score.hip — branch-rollout step-kernel instantiations (FUSE = 3, qs_score:
+// candidate action sequences from the handle's state, nothing stored to it) for
+// QS_TASK_MULTIHOVER.
+#include "step_launch_impl.h"
+
+QS_INSTANTIATE_LAUNCH_SCORE(QS_TASK_MULTIHOVER)

@@ -55,12 +55,17 @@ class QsStepOut(ctypes.Structure):
                 ("actions_out", ctypes.c_void_p)]
 
 
+class QsScoreOut(ctypes.Structure):
+    """include/quadswarm.h qs_score_out: the per-candidate summary of qs_score."""
+    _fields_ = [("ret", ctypes.c_void_p), ("first_done", ctypes.c_void_p)]
+
+
 EPISODE_DTYPE = np.dtype([("ret", "<f8"), ("len", "<i4"), ("env", "<i4"), ("seq", "<i8")])
 
 # Every symbol include/quadswarm.h declares (tests check the .so exports them).
 ABI_VERSION = 4   # include/quadswarm.h QS_ABI_VERSION
 EXPORTS = ("qs_create", "qs_destroy", "qs_last_error", "qs_abi_version", "qs_get_dims", "qs_reset",
-           "qs_reset_envs", "qs_step", "qs_step_many", "qs_step_seq", "qs_launch_counts", "qs_state_io", "qs_episode_log", "qs_reset_error", "qs_calib_copy",
+           "qs_reset_envs", "qs_step", "qs_step_many", "qs_step_seq", "qs_score_depth", "qs_score", "qs_launch_counts", "qs_state_io", "qs_episode_log", "qs_reset_error", "qs_calib_copy",
            # include/qs_learner.h
            "qs_gae", "qs_adam_gated", "qs_adam_commit", "qs_ppo_heads", "qs_ppo_heads_work_bytes",
            "qs_mlp_bias_tanh", "qs_mlp_bwd_blocks", "qs_mlp_tanh_bwd", "qs_mlp_sum_partials",
@@ -122,6 +127,9 @@ def load():
     L.qs_step.argtypes = [vp, vp, ctypes.POINTER(QsStepOut), vp]
     L.qs_step_many.argtypes = [vp, i32, ctypes.POINTER(QsStepOut), vp]
     L.qs_step_seq.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(QsStepOut), vp]
+    if hasattr(L, "qs_score"):   # (a QS_DEV_LIB build from before the entry points: A/B runs)
+        L.qs_score_depth.argtypes = [vp]
+        L.qs_score.argtypes = [vp, i32, i32, ctypes.POINTER(vp), ctypes.POINTER(QsStepOut), ctypes.POINTER(QsScoreOut), vp]
     if hasattr(L, "qs_launch_counts"):   # (a QS_DEV_LIB build from before the entry point: A/B runs)
         L.qs_launch_counts.argtypes = [vp, ctypes.POINTER(i64)]
     L.qs_state_io.argtypes = [vp, i32, vp, i32, vp]
@@ -190,7 +198,7 @@ def load():
     L.qs_rms_update.argtypes = [i64, ctypes.c_int32] + [vp] * 7
     L.qs_rms_normalize.argtypes = [i64, ctypes.c_int32, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp]
     for name in EXPORTS:
-        if name == "qs_launch_counts" and not hasattr(L, name):
+        if name in ("qs_launch_counts", "qs_score_depth", "qs_score") and not hasattr(L, name):
             continue   # (a QS_DEV_LIB build from before the entry point)
         if name not in ("qs_last_error", "qs_learner_last_error", "qs_rms_last_error", "qs_ppo_small_last_error",
                         "qs_rollout_last_error"):

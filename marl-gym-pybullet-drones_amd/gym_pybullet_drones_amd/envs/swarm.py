@@ -261,6 +261,77 @@ class QuadSwarm:
             L.check(self.lib.qs_step_seq(self._h, n, ptrs, arr, self._stream()), "qs_step_seq")
         return [res for _, res in recs]
 
+    # ------------------------------------------------------- branch rollouts
+    def score_depth(self):
+        """The longest candidate (in steps) one `score` call takes on this swarm
+        (qs_score_depth); 0: this swarm cannot score (a layout whose reset draws
+        can be rejected, or the Flock / Meetup / LeaderFollower tasks)."""
+        return int(self.lib.qs_score_depth(self._h))
+
+    _SCORE_OUTS = ("obs", "reward", "terminated", "truncated", "terminal_obs", "reasons", "actions_out")
+
+    def score(self, actions, outs=None, *, ret=None, first_done=None):
+        """Run C candidate action sequences of n steps each from the swarm's current
+        state in one launch, and leave the swarm exactly as it was (qs_score): no
+        state, history, episode log or counter changes.  Virtual env (c, e) starts
+        from env e and follows candidate c; its per-step outputs are, bit for bit,
+        what `step_many(outs, actions=actions[:, c])` would write from this state.
+
+        actions: one (n, C, E, D, A) float32 tensor, whose slices are passed as they
+        are (no copy), or a list of n (C, E, D, A) tensors (4-byte alignment will do;
+        steps may share a tensor).  outs: None, or one dict of step()'s output
+        keywords per step, each buffer stacked over the candidates (obs (C, E, D, O),
+        reward (C, E), ...); an output that is not named is not written.  ret:
+        (C, E) float64, the rewards of steps 0 .. the candidate's first done step
+        (all n if none), summed in step order; first_done: (C, E) int32, that step,
+        or n.  At least one output must be named, none may overlap another or an
+        action tensor, and 1 <= n <= score_depth()."""
+        E, D, A, O = self.num_envs, self.num_drones, self.act_dim, self.obs_dim
+        if isinstance(actions, torch.Tensor):
+            if actions.dim() != 5:
+                raise ValueError(f"actions must be (n, C, {E}, {D}, {A}) or a list of (C, {E}, {D}, {A}) tensors")
+            acts = [actions[j] for j in range(actions.shape[0])]
+        else:
+            acts = list(actions)
+        n = len(acts)
+        if n < 1 or not isinstance(acts[0], torch.Tensor) or acts[0].dim() != 4:
+            raise ValueError(f"actions must hold at least one step of shape (C, {E}, {D}, {A})")
+        C = acts[0].shape[0]
+        for a in acts:
+            if (not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or not a.is_contiguous()
+                    or a.device != self.device or tuple(a.shape) != (C, E, D, A)):
+                raise ValueError(f"actions: every step must be a contiguous float32 ({C},{E},{D},{A}) tensor on {self.device}")
+        want = dict(obs=(torch.float32, C * E * D * O), reward=(self.rdtype, C * E), terminated=(torch.uint8, C * E),
+                    truncated=(torch.uint8, C * E), terminal_obs=(torch.float32, C * E * D * O),
+                    reasons=(torch.uint8, C * E * D), actions_out=(torch.float32, C * E * D * A),
+                    ret=(torch.float64, C * E), first_done=(torch.int32, C * E))
+
+        def buf(t, what):
+            if t is None:
+                return None
+            dt, numel = want[what]
+            if (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous() or t.numel() < numel
+                    or t.device != self.device):
+                raise ValueError(f"{what} must be a contiguous {dt} tensor of >= {numel} elements on {self.device}")
+            return L.ptr(t)
+
+        arr = None
+        if outs is not None:
+            if len(outs) != n:
+                raise ValueError(f"outs must hold {n} steps, one dict each")
+            recs = []
+            for kw in outs:
+                unknown = set(kw) - set(self._SCORE_OUTS)
+                if unknown:
+                    raise ValueError(f"outs: unknown output {sorted(unknown)}")
+                recs.append(L.QsStepOut(*[buf(kw.get(k), k) for k in self._SCORE_OUTS]))
+            arr = (L.QsStepOut * n)(*recs)
+        so = None
+        if ret is not None or first_done is not None:
+            so = ctypes.byref(L.QsScoreOut(buf(ret, "ret"), buf(first_done, "first_done")))
+        ptrs = (ctypes.c_void_p * n)(*[a.data_ptr() for a in acts])
+        L.check(self.lib.qs_score(self._h, n, C, ptrs, arr, so, self._stream()), "qs_score")
+
     def launch_counts(self):
         """(general, hot): the multi-step launches made so far on the general kernel
         instances and on the shape-specialised one (qs_launch_counts; QS_HOT_SHAPE=0

@@ -106,6 +106,7 @@ class SwarmVecEnv(VecEnv):
         super().__init__(num_envs, observation_space_for(self.swarm), action_space_for(self.swarm))
         self._actions = None
         self._rollout_bufs = {}   # rollout_t's output buffers, by step count
+        self._score_bufs = {}     # score_t's, by (steps, candidates, per_step)
         self.NUM_DRONES = self.swarm.num_drones
         self.CTRL_FREQ = self.swarm.ctrl_freq
         self.CTRL_TIMESTEP = 1.0 / self.CTRL_FREQ
@@ -192,6 +193,39 @@ class SwarmVecEnv(VecEnv):
                 raise ValueError(f"{k} must be stacked over the {n} steps")
         sw.step_many([{k: v[j] for k, v in out.items()} for j in range(n)], actions=actions)
         return out["obs"], out["reward"], out["terminated"], out["truncated"]
+
+    def score_t(self, actions, per_step=False):
+        """Score C candidate action sequences from the envs' current state without
+        stepping them (QuadSwarm.score): `actions` is a (n, C, E, D, A) device
+        tensor.  Returns (ret (C, E) float64, first_done (C, E) int32): candidate
+        c's reward summed over its steps up to env e's first done step, and that
+        step (n if the env was never done).  per_step=True: also the stacked
+        (reward, terminated, truncated), each (n, C, E).  One launch, no host sync;
+        the episode log, the counters and the state are untouched.  The buffers
+        are allocated once per shape and returned again by every later call of
+        that shape."""
+        sw = self.swarm
+        if actions.dim() != 5:
+            raise ValueError(f"actions must be a (n, C, {sw.num_envs}, {sw.num_drones}, {sw.act_dim}) tensor")
+        n, C = actions.shape[0], actions.shape[1]
+        key = (n, C, bool(per_step))
+        own = self._score_bufs.get(key)
+        if own is None:
+            kw = dict(device=sw.device)
+            own = dict(ret=torch.zeros((C, sw.num_envs), dtype=torch.float64, **kw),
+                       first_done=torch.zeros((C, sw.num_envs), dtype=torch.int32, **kw))
+            if per_step:
+                own.update(reward=torch.zeros((n, C, sw.num_envs), dtype=sw.rdtype, **kw),
+                           terminated=torch.zeros((n, C, sw.num_envs), dtype=torch.uint8, **kw),
+                           truncated=torch.zeros((n, C, sw.num_envs), dtype=torch.uint8, **kw))
+            self._score_bufs[key] = own
+        outs = None
+        if per_step:
+            outs = [{k: own[k][j] for k in ("reward", "terminated", "truncated")} for j in range(n)]
+        sw.score(actions, outs, ret=own["ret"], first_done=own["first_done"])
+        if per_step:
+            return own["ret"], own["first_done"], own["reward"], own["terminated"], own["truncated"]
+        return own["ret"], own["first_done"]
 
     # -------------------------------------------- checkpoint RNG (MP:203-270)
     def get_env_random_state(self):
