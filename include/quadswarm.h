@@ -335,6 +335,75 @@ int qs_score_depth(const qs_handle* h);
 int qs_score(qs_handle* h, int n, int C, const float* const* actions,
              const qs_step_out* outs, const qs_score_out* score, void* stream);
 
+/* MPPI planner tick on top of qs_score: sample C candidate sequences round a
+ * nominal one, score them from the handle's current state, and fold them back
+ * into the nominal by their softmax weights, all on the device.  (New entry
+ * points of ABI 4, like qs_step_seq.)
+ *
+ * A planner is bound to one handle, which must outlive it, and owns its device
+ * buffers (qs_mppi_buffers; stable until qs_mppi_destroy).  Every call but
+ * create / destroy / buffers is stream-ordered and asynchronous, reads nothing
+ * back to the host and may be captured into a graph; the tick counter lives on
+ * the device, so a replayed graph draws new noise each time.  No float atomics:
+ * the same inputs give the same bytes.  Like a handle, a planner is used from
+ * one host thread at a time.
+ *
+ *  - qs_mppi_sample.  One Philox4x32-10 call per (step j, candidate c, env e,
+ *    drone d): key = seed, counter = (low word of *tick, env_offset + e,
+ *    c · 32 + j, (3 << 24) | d).  Word i gives u_i = ((x_i >> 8) + 1) · 2^-24 in
+ *    (0, 1]; z0, z1 = sqrt(-2 ln u0) · (cos, sin)(2π u1) and z2, z3 likewise from
+ *    u2, u3 (float32).  candidates[j][0][e][d][a] = nominal[j][e][d][a] as it is;
+ *    for c > 0, clamp(nominal + sigma[a] · z_a, lo, hi), the sum left out where
+ *    sigma[a] = 0.  The counter holds the global env id, so the noise does not
+ *    depend on how envs are sharded.
+ *  - qs_mppi_update.  Per env e, in double: s_c = ret[c][e] - (first_done[c][e]
+ *    < n ? done_penalty : 0); best[e] = the lowest c with the largest s;
+ *    lambda > 0: weights[c][e] = exp((s_c - s_best) / lambda) / sum over c;
+ *    lambda = 0: 1 at best, 0 elsewhere.  new[j] = (float) sum over c of
+ *    weights[c] · candidates[j][c] (lambda = 0: the best candidate's row, bit for
+ *    bit); action = new[0]; nominal[j] = new[j + 1] for j < n - 1 and
+ *    nominal[n - 1] = new[n - 1] (hold); *tick += 1.  Two launches.  It reads
+ *    candidates, ret and first_done as they are: a caller may fill them itself.
+ *  - qs_mppi_plan = sample, qs_score(h, n, C, candidates, NULL, {ret,
+ *    first_done}), update.  QS_E_STATE before qs_reset, with nothing launched.
+ *  - qs_mppi_reset copies `nominal` (device, [n][E][D][A]; NULL: zeros) into the
+ *    planner and sets *tick = 0.  A new planner is in that state with zeros.
+ *  - qs_mppi_create refusals (QS_E_INVALID, *out untouched): a handle with
+ *    qs_score_depth(h) = 0, horizon outside 1 .. qs_score_depth(h), candidates
+ *    < 2 or > 2^27, lo >= hi, a negative or non-finite sigma, lambda or
+ *    done_penalty, and sizes beyond the 32-bit offsets qs_score refuses.       */
+typedef struct qs_mppi_spec {
+  int32_t horizon;      /* n: 1 .. qs_score_depth(h)                              */
+  int32_t candidates;   /* C >= 2; candidate 0 is the nominal itself, unperturbed */
+  float sigma[4];       /* noise std per action component (first A used), >= 0    */
+  float lo, hi;         /* candidates are clipped to [lo, hi]; lo < hi            */
+  double lambda;        /* temperature; 0 = greedy (arg max, lowest c on ties)    */
+  double done_penalty;  /* subtracted from a candidate's score for env e when its
+                           first_done[c][e] < n                                   */
+  uint64_t seed;
+} qs_mppi_spec;
+
+typedef struct qs_mppi_bufs { /* device pointers owned by the planner           */
+  float* nominal;       /* [n][E][D][A]                                          */
+  float* candidates;    /* [n][C][E][D][A]  (what qs_score reads)                */
+  double* ret;          /* [C][E]  qs_score's ret                                */
+  int32_t* first_done;  /* [C][E]                                                */
+  double* weights;      /* [C][E]  normalised; greedy: 1 at best, 0 elsewhere    */
+  int32_t* best;        /* [E]     arg max of the penalised score, lowest c      */
+  float* action;        /* [E][D][A] the first step of the updated nominal       */
+  uint64_t* tick;       /* [1]     device counter, +1 per update                 */
+} qs_mppi_bufs;
+
+typedef struct qs_mppi qs_mppi;
+
+int qs_mppi_create(qs_handle* h, const qs_mppi_spec* spec, qs_mppi** out);
+int qs_mppi_destroy(qs_mppi* p);
+int qs_mppi_buffers(const qs_mppi* p, qs_mppi_bufs* out);
+int qs_mppi_reset(qs_mppi* p, const float* nominal, void* stream);
+int qs_mppi_sample(qs_mppi* p, void* stream);
+int qs_mppi_update(qs_mppi* p, void* stream);
+int qs_mppi_plan(qs_mppi* p, void* stream);
+
 /* Multi-step launches this handle has made so far (host, no device work):
  * out[0] on the general multi-step kernel instances, out[1] on the
  * shape-specialised one.  The specialised instance serves synthetic-policy

@@ -21,6 +21,7 @@
 #include "step_fuse.h"
 #include "step_score.h"
 #include "step_trunc.h"
+#include "planner_link.h"
 
 static_assert(qs::kFuseMax == qs::kMaxFuse, "step_fuse.h and step_kernel.h disagree on the fusion depth");
 static_assert(qs::kObsPipeMaxRow == qs::kObsPipeMaxO && qs::kObsPipeRows == qs::kBlock,
@@ -684,6 +685,16 @@ template <class T> static int score_impl(qs_handle* h, int n, int C, const float
   if (score) { P.ret = (double*)score->ret; P.first_done = score->first_done; }
   return launch_kernel<T, 3>(h, P, st, nullptr, false);
 }
+
+// planner.hip's view of a handle (planner_link.h).
+namespace qs {
+void handle_info(const qs_handle* h, HandleInfo* out) {
+  out->device = h->device;
+  out->env_offset = h->spec.env_offset;
+  out->reset_done = h->reset_done;
+}
+int set_last_error(int code, const std::string& msg) { return fail(code, msg); }
+}  // namespace qs
 
 extern "C" {
 

@@ -14,6 +14,7 @@ Reference semantics it implements (paths relative to gym_pybullet_drones/):
                                        vectorized_env/subproc_vec_env.py:188-206
 """
 import ctypes
+import weakref
 from dataclasses import dataclass
 from typing import Optional
 
@@ -159,6 +160,8 @@ class QuadSwarm:
 
     def close(self):
         if getattr(self, "_h", None):
+            for planner in list(getattr(self, "_planners", ())):
+                planner.close()
             torch.cuda.synchronize(self.device)
             self.lib.qs_destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -332,6 +335,17 @@ class QuadSwarm:
         ptrs = (ctypes.c_void_p * n)(*[a.data_ptr() for a in acts])
         L.check(self.lib.qs_score(self._h, n, C, ptrs, arr, so, self._stream()), "qs_score")
 
+    def mppi(self, horizon, candidates, sigma, lo=-1.0, hi=1.0, lam=1.0, done_penalty=0.0, seed=0):
+        """An `MPPIPlanner` on this swarm (qs_mppi_create): `candidates` action
+        sequences of `horizon` steps (1 .. score_depth()) are drawn round a nominal
+        one with per-component noise `sigma` (a number or one per action component),
+        clipped to [lo, hi], scored from the swarm's current state and folded back
+        by their softmax weights at temperature `lam` (0: the best one wins);
+        `done_penalty` is taken off a candidate that ends an episode."""
+        planner = MPPIPlanner(self, horizon, candidates, sigma, lo, hi, lam, done_penalty, seed)
+        self.__dict__.setdefault("_planners", weakref.WeakSet()).add(planner)   # close() ends them first
+        return planner
+
     def launch_counts(self):
         """(general, hot): the multi-step launches made so far on the general kernel
         instances and on the shape-specialised one (qs_launch_counts; QS_HOT_SHAPE=0
@@ -379,3 +393,107 @@ class QuadSwarm:
         v = ctypes.c_int(0)
         L.check(self.lib.qs_reset_error(self._h, ctypes.byref(v)), "qs_reset_error")
         return v.value
+
+
+class _DeviceSpan:
+    """A span of the planner's device memory, as `torch.as_tensor` reads it
+    (__cuda_array_interface__ version 2): the tensor views the memory, no copy."""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False),
+                                         "version": 2, "strides": None}
+
+
+class MPPIPlanner:
+    """The native MPPI tick round `QuadSwarm.score` (qs_mppi_*, include/quadswarm.h).
+
+    `sample()` draws `candidates` sequences round `nominal` (candidate 0 is the
+    nominal itself), `update()` weighs them by the scores in `ret` / `first_done`,
+    writes the weighted mean, shifted by one step, back to `nominal` and its first
+    step to `action`; `plan()` is sample, score from the swarm's current state,
+    update.  Every call is a few launches on the current stream with no host
+    sync, and may be captured into a graph together with the `step` that runs
+    `action`: the tick counter that keys the noise lives on the device.
+
+    The buffers are torch tensors that view the planner's device memory (no
+    copies; they dangle after `close()`): nominal (n, E, D, A), candidates
+    (n, C, E, D, A), ret (C, E) float64, first_done (C, E) int32, weights (C, E)
+    float64, best (E,) int32, action (E, D, A), tick (1,) (the uint64 counter,
+    viewed as int64).  The swarm must outlive the planner."""
+
+    def __init__(self, swarm, horizon, candidates, sigma, lo=-1.0, hi=1.0, lam=1.0, done_penalty=0.0, seed=0):
+        self.swarm, self.lib = swarm, swarm.lib
+        if not hasattr(self.lib, "qs_mppi_create"):
+            raise L.QuadSwarmError(f"{L.LIB_PATH} has no qs_mppi_create: rebuild the HIP extension")
+        A = swarm.act_dim
+        sig = [float(sigma)] * A if np.isscalar(sigma) else [float(s) for s in sigma]
+        if len(sig) != A:
+            raise ValueError(f"sigma must be a number or one per action component ({A})")
+        spec = L.QsMppiSpec()
+        spec.horizon, spec.candidates = int(horizon), int(candidates)
+        for a in range(A):
+            spec.sigma[a] = sig[a]
+        spec.lo, spec.hi, spec.lambda_, spec.done_penalty = float(lo), float(hi), float(lam), float(done_penalty)
+        spec.seed = int(seed)
+        self.spec = spec
+        self.horizon, self.num_candidates = int(horizon), int(candidates)
+        self._p = ctypes.c_void_p()
+        self._stepper = swarm.step   # what step_t runs the action with (SwarmVecEnv.mppi: its step_t)
+        with torch.cuda.device(swarm.device):
+            L.check(self.lib.qs_mppi_create(swarm._h, ctypes.byref(spec), ctypes.byref(self._p)), "qs_mppi_create")
+        bufs = L.QsMppiBufs()
+        L.check(self.lib.qs_mppi_buffers(self._p, ctypes.byref(bufs)), "qs_mppi_buffers")
+        n, C, E, D = self.horizon, self.num_candidates, swarm.num_envs, swarm.num_drones
+
+        def view(ptr, shape, typestr):
+            return torch.as_tensor(_DeviceSpan(ptr, shape, typestr), device=swarm.device)
+
+        self.nominal = view(bufs.nominal, (n, E, D, A), "<f4")
+        self.candidates = view(bufs.candidates, (n, C, E, D, A), "<f4")
+        self.ret = view(bufs.ret, (C, E), "<f8")
+        self.first_done = view(bufs.first_done, (C, E), "<i4")
+        self.weights = view(bufs.weights, (C, E), "<f8")
+        self.best = view(bufs.best, (E,), "<i4")
+        self.action = view(bufs.action, (E, D, A), "<f4")
+        self.tick = view(bufs.tick, (1,), "<i8")
+
+    def _stream(self):
+        return self.swarm._stream()
+
+    def reset(self, nominal=None):
+        """Set the nominal sequence ((n, E, D, A) float32 on the device; None: zeros) and tick = 0."""
+        if nominal is not None:
+            if (not isinstance(nominal, torch.Tensor) or nominal.dtype != torch.float32 or not nominal.is_contiguous()
+                    or nominal.device != self.swarm.device or tuple(nominal.shape) != tuple(self.nominal.shape)):
+                raise ValueError(f"nominal must be a contiguous float32 {tuple(self.nominal.shape)} tensor on "
+                                 f"{self.swarm.device}")
+        L.check(self.lib.qs_mppi_reset(self._p, L.ptr(nominal), self._stream()), "qs_mppi_reset")
+
+    def sample(self):
+        L.check(self.lib.qs_mppi_sample(self._p, self._stream()), "qs_mppi_sample")
+
+    def update(self):
+        L.check(self.lib.qs_mppi_update(self._p, self._stream()), "qs_mppi_update")
+
+    def plan(self):
+        """One planner tick from the swarm's current state; returns `action`."""
+        L.check(self.lib.qs_mppi_plan(self._p, self._stream()), "qs_mppi_plan")
+        return self.action
+
+    def step_t(self, **bufs):
+        """One receding-horizon tick: `plan()`, then the control step that runs
+        `action` (the swarm's `step`, or `SwarmVecEnv.step_t`), with its return."""
+        self.plan()
+        return self._stepper(self.action, **bufs)
+
+    def close(self):
+        if getattr(self, "_p", None):
+            torch.cuda.synchronize(self.swarm.device)
+            self.lib.qs_mppi_destroy(self._p)
+            self._p = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

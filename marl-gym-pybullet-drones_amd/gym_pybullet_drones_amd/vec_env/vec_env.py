@@ -227,6 +227,15 @@ class SwarmVecEnv(VecEnv):
             return own["ret"], own["first_done"], own["reward"], own["terminated"], own["truncated"]
         return own["ret"], own["first_done"]
 
+    def mppi(self, horizon, candidates, sigma, **kw):
+        """An `MPPIPlanner` on these envs (QuadSwarm.mppi, same arguments).  Its
+        `step_t(**bufs)` is one receding-horizon tick: `plan()` from the envs'
+        current state, then `step_t(planner.action, **bufs)`, with step_t's
+        return; a few launches on the current stream, no host sync."""
+        planner = self.swarm.mppi(horizon, candidates, sigma, **kw)
+        planner._stepper = self.step_t
+        return planner
+
     # -------------------------------------------- checkpoint RNG (MP:203-270)
     def get_env_random_state(self):
         """Counter-based RNG: the stream state is (seed, per-env counters)."""
