@@ -418,6 +418,20 @@ int qs_mppi_plan(qs_mppi* p, void* stream);
  * ends.  (A new entry point of ABI 4, like qs_step_seq.) */
 int qs_launch_counts(const qs_handle* h, int64_t out[2]);
 
+/* Ring launches this handle has made so far (host, no device work).  A launch
+ * of the shape-specialised instance goes on past its distinct output sets, up
+ * to QS_MAX_FUSED_STEPS of them, while the further steps write exactly those
+ * sets again in the same order (a rollout into a ring of buffers): step k of
+ * the launch writes set k mod P, and every set ends up holding what the last
+ * step that wrote it produced, as after single steps.  *launches: such
+ * launches (they also count under qs_launch_counts' out[1]); *steps: the
+ * control steps they held.  At most 1024 steps to a launch (QS_RING_MAX_STEPS
+ * at qs_create lowers it); QS_RING_LAUNCH=0 at qs_create cuts every launch at
+ * the first repeated set, as all other shapes are cut.  A capture's kernel node
+ * counts once, with the steps it holds when the capture ends.  (An additive
+ * entry point of ABI 4.) */
+int qs_ring_counts(const qs_handle* h, int64_t* launches, int64_t* steps);
+
 /* Copy a state block between the handle and `buf` (device pointer).
  * dir = 0: handle → buf (get), dir = 1: buf → handle (set). */
 int qs_state_io(qs_handle* h, int block, void* buf, int dir, void* stream);

@@ -193,6 +193,17 @@ struct qs_handle {
   bool hot_shape = true;
   int64_t launches[2] = {0, 0};
   int fuse_kind = -1;
+  // A hot-shape launch goes on past its distinct output sets while the further
+  // steps write them again in order (step_fuse.h, can_wrap; the ring instance,
+  // step_mh_ring.hip); QS_RING_LAUNCH=0 cuts such a launch as before (the A/B
+  // switch), QS_RING_MAX_STEPS (1 .. qs::kRingMaxSteps) caps its steps.  ring[]:
+  // ring launches made so far and the steps they held (qs_ring_counts); a
+  // capture's node counts once, with the steps it holds after its last wrap
+  // (fuse_ring_steps: how many of ring[1] are the node's of h->fuse).
+  bool ring_launch = true;
+  int ring_max = qs::kRingMaxSteps;
+  int64_t ring[2] = {0, 0};
+  int fuse_ring_steps = 0;
   qs::FuseGroup fuse;
   qs::ParamsMany<float> fuse_pf;
   qs::ParamsMany<double> fuse_pd;
@@ -286,6 +297,20 @@ struct LaunchInfo {
   size_t lds = 0;
 };
 
+// What qs::hot_shape_ok judges, for a multi-step launch over P.io[0 .. P.nsteps-1]
+// (P.nsteps <= qs::kMaxFuse; P.obs_pipe decided); masks: the steps' output masks.
+template <class T>
+static qs::HotShape hot_shape_of(const qs_handle* h, const qs::ParamsMany<T>& P, unsigned masks[qs::kMaxFuse]) {
+  const qs_spec& s = h->spec;
+  for (int j = 0; j < P.nsteps; ++j) {
+    const qs::StepIO<T>& o = P.io[j];
+    masks[j] = qs::out_mask(qs::FuseOuts{{o.obs, o.rew, o.term, o.trunc, o.tobs, o.reasons, o.act_out}});
+  }
+  return qs::HotShape{s.task, s.act_type, fixed_ctrl_freq(s), s.physics, s.aux_forces, s.flags, P.D, P.E, P.EPB,
+                      P.reject_free != 0, P.reset_queue != nullptr, P.reset_pre != nullptr, P.wave_reduce != 0,
+                      P.obs_pipe != 0};
+}
+
 // Grid, LDS plan (P.stage_rows) and the kernel of a launch; FUSE = 1: the
 // multi-step instance over P.io[0 .. P.nsteps-1] (MODE_STEP, no trainer actions,
 // no deferred reset queue: the callers see to that); FUSE = 2: the same over the
@@ -311,13 +336,7 @@ static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t
       // the shape-specialised instance, decided per launch over all its steps (so a
       // capture's node is re-decided, either way, each time a step joins it)
       unsigned masks[qs::kMaxFuse];
-      for (int j = 0; j < P.nsteps; ++j) {
-        const qs::StepIO<T>& o = P.io[j];
-        masks[j] = qs::out_mask(qs::FuseOuts{{o.obs, o.rew, o.term, o.trunc, o.tobs, o.reasons, o.act_out}});
-      }
-      const qs::HotShape hs{s.task, s.act_type, fixed_cf, s.physics, s.aux_forces, s.flags, P.D, P.E, P.EPB,
-                            P.reject_free != 0, P.reset_queue != nullptr, P.reset_pre != nullptr, P.wave_reduce != 0,
-                            P.obs_pipe != 0};
+      const qs::HotShape hs = hot_shape_of(h, P, masks);
       const bool hot = h->hot_shape && qs::hot_shape_ok(hs, masks, P.nsteps);
       if (kind) *kind = hot ? 1 : 0;
       if (hot) {
@@ -361,6 +380,40 @@ static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t
 template <class T> static int launch_many(qs_handle* h, qs::ParamsMany<T>& P, hipStream_t st, LaunchInfo* info = nullptr,
                                           bool select_only = false, int* kind = nullptr) {
   return launch_kernel<T, 1>(h, P, st, info, select_only, kind);
+}
+
+// A ring launch (step_fuse.h, can_wrap): `total` steps over the P.nsteps distinct
+// output sets of P (the period), on the ring instance.  Grid, LDS plan, the fast
+// obs path and the shape are decided over the distinct sets, as for the launch
+// of those alone; R receives the arguments (what a graph kernel node holds).
+// QS_E_INVALID if qs::ring_shape_ok refuses (the callers wrap only what it accepts).
+template <class T> static int launch_ring(qs_handle* h, qs::ParamsMany<T>& P, int total, hipStream_t st, qs::ParamsRing<T>& R,
+                                          LaunchInfo* info = nullptr, bool select_only = false) {
+  LaunchInfo li;
+  const int rc = launch_many(h, P, st, &li, /*select_only=*/true);
+  if (rc != QS_OK) return rc;
+  unsigned masks[qs::kMaxFuse];
+  const qs::HotShape hs = hot_shape_of(h, P, masks);
+  if (!h->hot_shape || !h->ring_launch || !qs::ring_shape_ok(hs, masks, P.nsteps, total))
+    return fail(QS_E_INVALID, "launch: not a ring launch");
+  std::memset(&R, 0, sizeof(R));
+  static_cast<qs::ParamsMany<T>&>(R) = P;
+  R.period = P.nsteps;
+  R.nsteps = total;
+  const void* fn = nullptr;
+  qs::launch_ring<T>(h->spec.physics, li.grid, li.lds, st, R, &fn, select_only);
+  if (info) { info->fn = fn; info->grid = li.grid; info->lds = li.lds; }
+  if (select_only) return QS_OK;
+  HIP_TRY(hipGetLastError());
+  h->launches[1] += 1;
+  h->ring[0] += 1;
+  h->ring[1] += total;
+  return QS_OK;
+}
+// Would the launch of P's distinct sets run the hot shape (so that it may wrap)?
+template <class T> static bool ring_eligible(qs_handle* h, qs::ParamsMany<T>& P, hipStream_t st) {
+  int kind = 0;
+  return h->ring_launch && P.nsteps >= 2 && launch_many(h, P, st, nullptr, /*select_only=*/true, &kind) == QS_OK && kind == 1;
 }
 
 // Steps per launch of qs_step_seq: the handle's depth, capped where the action
@@ -487,16 +540,27 @@ template <class T> static bool try_coalesce(qs_handle* h, const qs_step_out& o, 
   if (hipGraphNodeGetDependentNodes(node, nullptr, &dependents) != hipSuccess) { (void)hipGetLastError(); return false; }
   if (dependents != 0) return false;
   const qs::FuseOuts fo = to_outs(o);
-  if (!g.can_append(fo, h->fuse_depth)) return false;
-  qs::ParamsMany<T> P = fuse_params<T>(h);
-  P.io[g.count] = to_io<T>(o);
-  P.nsteps = g.count + 1;
+  // a new output set while the node has not wrapped; else the set that is due in its ring
+  const bool grow = g.period == 0 && g.can_append(fo, h->fuse_depth);
+  if (!grow && !(h->ring_launch && g.can_wrap(fo, h->fuse_depth, h->ring_max))) return false;
+  qs::ParamsMany<T> P = fuse_params<T>(h);   // (P.nsteps counts the distinct sets)
+  if (grow) {
+    P.io[g.count] = to_io<T>(o);
+    P.nsteps = g.count + 1;
+  }
   LaunchInfo li;
   int kind = 0;
-  if (launch_many(h, P, st, &li, /*select_only=*/true, &kind) != QS_OK || !li.fn) return false;
+  qs::ParamsRing<T> R;
+  void* args[1] = {&P};
+  if (grow) {
+    if (launch_many(h, P, st, &li, /*select_only=*/true, &kind) != QS_OK || !li.fn) return false;
+  } else {   // the node moves to (or stays on) the ring instance; a shape that is not hot cuts here
+    if (launch_ring(h, P, g.total + 1, st, R, &li, /*select_only=*/true) != QS_OK || !li.fn) return false;
+    kind = 1;
+    args[0] = &R;
+  }
   hipKernelNodeParams np;
   std::memset(&np, 0, sizeof(np));
-  void* args[1] = {&P};
   np.func = const_cast<void*>(li.fn);
   np.gridDim = dim3((unsigned)li.grid);
   np.blockDim = dim3(qs::kBlock);
@@ -504,7 +568,14 @@ template <class T> static bool try_coalesce(qs_handle* h, const qs_step_out& o, 
   np.kernelParams = args;   // (the runtime copies the arguments during the call)
   if (hipGraphKernelNodeSetParams(node, &np) != hipSuccess) { (void)hipGetLastError(); return false; }
   fuse_params<T>(h) = P;
-  g.append(fo);
+  if (grow) {
+    g.append(fo);
+  } else {
+    g.wrap();
+    if (h->fuse_ring_steps == 0) h->ring[0] += 1;
+    h->ring[1] += g.total - h->fuse_ring_steps;
+    h->fuse_ring_steps = g.total;
+  }
   // the node now names instance `kind`: it counts there, and no longer where it did
   if (h->fuse_kind >= 0) h->launches[h->fuse_kind] -= 1;
   h->launches[kind] += 1;
@@ -530,6 +601,7 @@ template <class T> static void note_capture(qs_handle* h, const qs::Params<T>& P
   out_sizes(h, sizes);
   h->fuse.begin(sizes, to_outs(o), c.id, (void*)st, (void*)c.deps[0]);
   h->fuse_kind = -1;   // a single step so far
+  h->fuse_ring_steps = 0;
   qs::ParamsMany<T>& F = fuse_params<T>(h);
   std::memset(&F, 0, sizeof(F));
   static_cast<qs::Params<T>&>(F) = P;
@@ -566,12 +638,20 @@ template <class T> static int step_many_impl(qs_handle* h, int n, const qs_step_
     if (g.count > 1) {
       P.nsteps = g.count;
       for (int k = 0; k < g.count; ++k) P.io[k] = to_io<T>(outs[j + k]);
-      rc = launch_many(h, P, st);
+      // then the steps that write the run's sets again in order, while the run is the hot shape's
+      if (j + g.total < n && g.can_wrap(to_outs(outs[j + g.total]), depth, h->ring_max) && ring_eligible(h, P, st))
+        while (j + g.total < n && g.can_wrap(to_outs(outs[j + g.total]), depth, h->ring_max)) g.wrap();
+      if (g.total > g.count) {
+        qs::ParamsRing<T> R;
+        rc = launch_ring(h, P, g.total, st, R);
+      } else {
+        rc = launch_many(h, P, st);
+      }
     } else {
       rc = launch<T>(h, P, st);
     }
     if (rc != QS_OK) return rc;
-    j += g.count;
+    j += g.total;
   }
   return QS_OK;
 }
@@ -755,6 +835,12 @@ int qs_create(const qs_spec* spec, int device, qs_handle** out) {
   }
   if (const char* v = getenv("QS_WAVE_REDUCE")) h->wave_reduce = std::strtol(v, nullptr, 10) != 0;   // read once, here
   if (const char* v = getenv("QS_HOT_SHAPE")) h->hot_shape = std::strtol(v, nullptr, 10) != 0;       // read once, here
+  if (const char* v = getenv("QS_RING_LAUNCH")) h->ring_launch = std::strtol(v, nullptr, 10) != 0;   // read once, here
+  if (const char* v = getenv("QS_RING_MAX_STEPS")) {                                                 // read once, here
+    char* end = nullptr;
+    const long k = std::strtol(v, &end, 10);
+    if (end != v) h->ring_max = (int)std::min<long>(std::max<long>(k, 1), qs::kRingMaxSteps);
+  }
   h->spec = s;
   h->spec.initial_xyzs = nullptr;
   h->device = device;
@@ -866,6 +952,13 @@ int qs_destroy(qs_handle* h) {
   void* ptrs[] = {h->st, h->env, h->hist, h->orig, h->log, h->err, h->stamps, h->rq, h->rpre, h->logw, h->log_sel};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   delete h;
+  return QS_OK;
+}
+
+int qs_ring_counts(const qs_handle* h, int64_t* launches, int64_t* steps) {
+  if (!h || !launches || !steps) return fail(QS_E_INVALID, "qs_ring_counts: null argument");
+  *launches = h->ring[0];
+  *steps = h->ring[1];
   return QS_OK;
 }
 

@@ -97,12 +97,31 @@ inline bool hot_shape_ok(const HotShape& s, const unsigned* out_masks, int nstep
   return true;
 }
 
+// A launch may go on past its distinct output sets when the further steps write
+// those sets again in the same order (a ring of P sets: step k of the launch
+// writes set k mod P).  Safe because a workgroup writes only its own envs' rows of
+// every output, a wave's stores to one address retire in program order, and
+// nothing in a launch reads what it wrote: after the launch every set holds what
+// the last step that wrote it produced, as after a chain of single steps.  Only
+// the ring instance of the kernel (step_kernel HOT = 2, step_mh_ring.hip) runs
+// such a launch, so only the hot shape wraps (ring_shape_ok); kRingMaxSteps caps
+// the steps of one launch.
+constexpr int kRingMaxSteps = 1024;
+
+// hot_shape_ok over the `period` distinct sets of a launch of `total` steps that
+// has wrapped at least once.
+inline bool ring_shape_ok(const HotShape& s, const unsigned* out_masks, int period, int total) {
+  return hot_shape_ok(s, out_masks, period) && total > period && total <= kRingMaxSteps;
+}
+
 struct FuseGroup {
   bool live = false;
   unsigned long long capture_id = 0;   // the stream capture the node belongs to
   void* stream = nullptr;
   void* node = nullptr;                // the kernel node that holds `count` steps
-  int count = 0;
+  int count = 0;                       // distinct output sets held (outs[0 .. count-1])
+  int period = 0;                      // 0 until a wrap; then the ring's length (= count, which no longer grows)
+  int total = 0;                       // steps held: count, plus the wrapped ones
   size_t bytes[kFuseOuts] = {0, 0, 0, 0, 0, 0, 0};   // size of each output a step writes
   FuseOuts outs[kFuseMax];
 
@@ -111,6 +130,8 @@ struct FuseGroup {
     node = nullptr;
     stream = nullptr;
     count = 0;
+    period = 0;
+    total = 0;
   }
 
   // A new group whose first step writes `o`.
@@ -119,6 +140,8 @@ struct FuseGroup {
     for (int i = 0; i < kFuseOuts; ++i) bytes[i] = sizes[i];
     outs[0] = o;
     count = 1;
+    period = 0;
+    total = 1;
     capture_id = id;
     stream = st;
     node = nd;
@@ -158,6 +181,35 @@ struct FuseGroup {
   void append(const FuseOuts& o) {
     outs[count] = o;
     count += 1;
+    total += 1;
+  }
+
+  static bool same_set(const FuseOuts& a, const FuseOuts& b) {
+    for (int i = 0; i < kFuseOuts; ++i)
+      if (a.p[i] != b.p[i]) return false;
+    return true;
+  }
+
+  // May a further step whose outputs `o` overlap the group's join it as the next
+  // step of a ring?  Only if it writes exactly the set that is due: all seven
+  // pointers, NULLs included, those of outs[total mod P], where P is the period
+  // (before the first wrap the number of sets held, and then the set due is
+  // outs[0]).  At least two sets, at most min(depth, kFuseMax) of them, and fewer
+  // than `max_total` (and kRingMaxSteps) steps so far.  Anything else cuts the
+  // launch: a set out of turn, one pointer that differs, a partial overlap, one
+  // buffer set reused every step (P = 1).  Once a group has wrapped it takes no
+  // new set: the caller asks can_append only while period == 0.
+  bool can_wrap(const FuseOuts& o, int depth, int max_total) const {
+    const int cap = depth < kFuseMax ? depth : kFuseMax;
+    const int lim = max_total < kRingMaxSteps ? max_total : kRingMaxSteps;
+    if (!live || count < 2 || count > cap || total < count || total >= lim) return false;
+    if (period == 0 ? total != count : period != count) return false;
+    return same_set(o, outs[total % count]);
+  }
+
+  void wrap() {
+    period = count;
+    total += 1;
   }
 };
 

@@ -321,6 +321,12 @@ template <class T> struct ParamsScore : ParamsSeq<T> {
   double* ret;           // [E] or NULL: the candidate's return up to its first done
   int32_t* first_done;   // [E] or NULL: that step, nsteps if none
 };
+// Arguments of the ring instances (step_kernel HOT = 2): nsteps may exceed
+// kMaxFuse, step k of the launch writes io[k mod period] (step_fuse.h, can_wrap).
+// Yet another type of its own: ParamsMany keeps its size.
+template <class T> struct ParamsRing : ParamsMany<T> {
+  int period;
+};
 template <class T, int FUSE>
 using KernelParams = std::conditional_t<FUSE == 3, ParamsScore<T>,
     std::conditional_t<FUSE == 2, ParamsSeq<T>, std::conditional_t<FUSE != 0, ParamsMany<T>, Params<T>>>>;
@@ -866,6 +872,11 @@ template <class T> __device__ __forceinline__ int launch_src_envs(const ParamsSc
 // HOT = 0, whose statements stand as they were (each hot form is chosen by a
 // compile-time test beside the statement it replaces), so the other instances
 // compile to the code they had.
+// HOT = 2 (step_mh_ring.hip): the HOT = 1 body for a launch whose steps cycle
+// through P.period output sets (ParamsRing; step_fuse.h, can_wrap): step ks
+// writes io[ks mod period], the index kept as a scalar that returns to 0 at the
+// period, and P.nsteps may be up to qs::kRingMaxSteps.  `pend` carries the
+// previous span's address, so nothing re-indexes the previous step.
 // QS_HOT_ITEMS (dev builds): each bit keeps one of those pieces, to measure it by
 // leaving it out — 1 shape, 2 outputs, 4 resets, 8 hoisted scalars, 16 rare tail.
 #ifndef QS_HOT_ITEMS
@@ -890,10 +901,11 @@ template <class V> __device__ __forceinline__ V* keep_sgpr(V* p) {
 }
 
 template <class T, int TASK, int ACT, int CF, int PHYS, int AUXM, int FUSE = 0, int HOT = 0>
-__global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
+__global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 2, ParamsRing<T>, KernelParams<T, FUSE>> P) {
   using F = M<T>;
   constexpr bool kFuse = FUSE != 0;
   constexpr bool kHot = HOT != 0;
+  constexpr bool kRing = HOT == 2;   // the hot shape over a ring of output sets (ParamsRing)
   static_assert(!kHot || (FUSE == 1 && TASK == QS_TASK_MULTIHOVER && CF != 0 && AUXM == 0), "hot shape: see above");
   constexpr bool kHotShape = kHot && (QS_HOT_ITEMS & 1) != 0, kHotOuts = kHot && (QS_HOT_ITEMS & 2) != 0;
   constexpr bool kHotReset = kHot && (QS_HOT_ITEMS & 4) != 0, kHotScal = kHot && (QS_HOT_ITEMS & 8) != 0;
@@ -1180,10 +1192,15 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
   // (a do-while whose condition is the constant false without FUSE: no loop
   // is emitted for the single-step instances)
   int ks = 0;
+  // ring: the output set of step ks, ks mod period (wave-uniform; back to 0 at the period)
+  [[maybe_unused]] int kr = 0;
+  [[maybe_unused]] int period_h = 0;
+  if constexpr (kRing) period_h = keep_sgpr(P.period);
 #pragma clang loop unroll(disable)
   do {
   StepIO<T> io{P.obs, P.rew, P.term, P.trunc, P.tobs, P.reasons, P.act_out};
-  if constexpr (kFuse) io = P.io[ks];
+  if constexpr (kRing) io = P.io[kr];
+  else if constexpr (kFuse) io = P.io[ks];
   if constexpr (kFuse) {   // what the next single-step launch would read back from its loads
     ep_ret0 = ep_ret_out;
     ep_len = ep_len_out;
@@ -2103,6 +2120,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(KernelParams<T, FUSE> P) {
     }
     wslot = wslot + 1 == H ? 0 : wslot + 1;
   }
+  if constexpr (kRing) kr = kr + 1 == period_h ? 0 : kr + 1;
   } while (kFuse && ++ks < launch_steps(P));   // control steps of this launch
   if constexpr (kPipe) {   // the last step's obs span
     if (pend != nullptr) {

@@ -21,4 +21,9 @@ bool launch_task(int act, int grid, size_t lds, hipStream_t st, const KernelPara
 template <class T>
 void launch_hot(int phys, int grid, size_t lds, hipStream_t st, const ParamsMany<T>& P, const void** fn = nullptr,
                 bool select_only = false);
+// The ring instance (step_kernel HOT = 2; step_mh_ring.hip) for a launch
+// qs::ring_shape_ok accepts: the hot shape, P.nsteps steps over P.period output sets.
+template <class T>
+void launch_ring(int phys, int grid, size_t lds, hipStream_t st, const ParamsRing<T>& P, const void** fn = nullptr,
+                 bool select_only = false);
 }  // namespace qs

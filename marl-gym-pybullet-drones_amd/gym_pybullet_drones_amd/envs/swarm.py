@@ -239,7 +239,9 @@ class QuadSwarm:
         slices are passed as they are (no copy).  Steps share a launch only while
         their output buffers are distinct and none of them reads as actions what
         another one writes; otherwise the launch is cut, so the result always
-        equals the single steps'.  Returns the steps' StepResults."""
+        equals the single steps'.  (A launch of the shape-specialised kernel also
+        keeps the steps that write its buffer sets again in the same order: see
+        `ring_counts`.)  Returns the steps' StepResults."""
         n = len(outs)
         acts = None
         if actions is not None:
@@ -353,6 +355,15 @@ class QuadSwarm:
         out = (ctypes.c_int64 * 2)()
         L.check(self.lib.qs_launch_counts(self._h, out), "qs_launch_counts")
         return int(out[0]), int(out[1])
+
+    def ring_counts(self):
+        """(launches, steps): the ring launches made so far and the control steps they
+        held (qs_ring_counts): hot-shape launches that went on past their distinct
+        output sets because the further steps wrote those sets again in order
+        (QS_RING_LAUNCH=0 at construction cuts them as before)."""
+        n, k = ctypes.c_int64(0), ctypes.c_int64(0)
+        L.check(self.lib.qs_ring_counts(self._h, ctypes.byref(n), ctypes.byref(k)), "qs_ring_counts")
+        return int(n.value), int(k.value)
 
     # ------------------------------------------------------------ state I/O
     def _state_buf(self, block):
