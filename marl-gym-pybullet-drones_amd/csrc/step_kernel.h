@@ -882,6 +882,14 @@ template <class T> __device__ __forceinline__ int launch_src_envs(const ParamsSc
 #ifndef QS_HOT_ITEMS
 #define QS_HOT_ITEMS 31
 #endif
+// QS_RING_ITEMS (dev builds), what the ring instance alone does about its stores
+// ("Ring launches"), each bit to be left out like QS_HOT_ITEMS': 1 the
+// action-history ring written once after the loop from hreg[] and not slot by slot
+// every step.  (Bit 2 was a placement of neighbouring env blocks on one XCD: tried
+// and not adopted)
+#ifndef QS_RING_ITEMS
+#define QS_RING_ITEMS 1
+#endif
 constexpr int kHotD = 8;   // = qs::kHotDrones (step_fuse.h), checked in quadswarm.hip
 // A launch-invariant scalar the loop needs, read before it and held in an SGPR: as
 // a plain kernel-argument read the backend re-issues the scalar load inside the
@@ -911,6 +919,8 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
   constexpr bool kHotReset = kHot && (QS_HOT_ITEMS & 4) != 0, kHotScal = kHot && (QS_HOT_ITEMS & 8) != 0;
   // (the tests are on the wave's ballot of `dn`, which the shape item's wave reduction forms)
   constexpr bool kHotTail = kHotShape && (QS_HOT_ITEMS & 16) != 0;
+  constexpr bool kRingHist = kRing && (QS_RING_ITEMS & 1) != 0;
+  static_assert(!kRing || CF != 0, "ring: the history lives in hreg[]");
   // a launch value: hot shape, the copy read before the loop (name_h below); else P's, read where it is used
 #define QS_LAUNCH_VAL(field) (kHotScal ? field##_h : P.field)
 #define QS_EPB (kHotShape ? kBlock / kHotD : P.EPB)
@@ -1287,7 +1297,8 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
       // lines; per-component dword stores left 16-B-strided partial lines)
       if (kHotOuts ? true : io.act_out != nullptr) store_act<A>(io.act_out + (size_t)a * A, act);
       // action_buffer.append(action) (BaseRLAviary.py:187): ring slot total % H
-      if constexpr (!kScore) store_act<A>(QS_LAUNCH_VAL(hist) + ((size_t)wslot * N + a) * A, act);
+      // (ring: the slots are written once, after the loop)
+      if constexpr (!kScore && !kRingHist) store_act<A>(QS_LAUNCH_VAL(hist) + ((size_t)wslot * N + a) * A, act);
       if constexpr (kPid && !kFuse) {   // PID integrators are final: store now, drains under the substeps
 #pragma unroll
         for (int i = 0; i < 9; ++i) SA.st(QS_F_PID_INT_POS + i, pid[i]);
@@ -2102,6 +2113,12 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
     // the next step's view of the ring: this step's action takes slot wslot
     // (the launches' `total % H`; total advances by one per step)
     if constexpr (kAged) {   // every entry ages by one step; this step's action is the newest older entry
+      // ring: the entry that ages out is what the next write slot holds; hreg[HR − 1]
+      // (the first write slot's content since the rotation) carries it to the stores after the loop
+      if constexpr (kRingHist) {
+#pragma unroll
+        for (int k = 0; k < A; ++k) hreg[HR - 1][k] = hreg[0][k];
+      }
 #pragma unroll
       for (int col = 0; col < HR - 1; ++col)
 #pragma unroll
@@ -2127,6 +2144,19 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
       float4 pv[kPipeIt];
       pend_read(pv);
       pend_store(pv, pend);
+    }
+  }
+  // ring: the action-history ring, once.  hreg[0 .. HR − 2] are the HR − 1 newest
+  // entries, oldest first, so hreg[j] belongs to slot wslot + 1 + j (mod HR; wslot is
+  // the next write slot, total % H), and hreg[HR − 1] holds that slot's own content
+  // (j = HR − 1 in the same formula).  All HR slots are stored: one that no step of
+  // the launch wrote gets back the bytes that were loaded from it.
+  if constexpr (kRingHist) {
+#pragma unroll
+    for (int j = 0; j < HR; ++j) {
+      int sl = wslot + 1 + j;
+      sl -= sl >= HR ? HR : 0;
+      store_act<A>(QS_LAUNCH_VAL(hist) + ((size_t)sl * N + a) * A, hreg[j]);
     }
   }
   if constexpr (kScore) {   // the candidate's score, by the env's first lane
