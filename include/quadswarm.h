@@ -404,6 +404,101 @@ int qs_mppi_sample(qs_mppi* p, void* stream);
 int qs_mppi_update(qs_mppi* p, void* stream);
 int qs_mppi_plan(qs_mppi* p, void* stream);
 
+/* CEM (cross-entropy method) planner tick on top of qs_score: per env, I
+ * iterations of "sample C candidate sequences round a mean with a per-element
+ * spread, score them from the handle's current state, refit mean and spread to
+ * the K best", all on the device.  (New entry points of ABI 4, like qs_mppi_*.)
+ *
+ * A planner is bound to one handle, which must outlive it, and owns its device
+ * buffers (qs_cem_buffers; stable until qs_cem_destroy).  Every call but
+ * create / destroy / buffers is stream-ordered and asynchronous, reads nothing
+ * back to the host and may be captured into a graph; the tick counter lives on
+ * the device, so a replayed graph draws new noise each time.  No float atomics
+ * and every sum in a fixed order: the same inputs give the same bytes.  Like a
+ * handle, a planner is used from one host thread at a time.  Every env plans
+ * independently of the others.
+ *
+ *  - qs_cem_begin.  std[j][e][d][a] = sigma[a] everywhere: the spread restarts
+ *    at every tick, only the mean carries over.
+ *  - qs_cem_sample(p, i).  One Philox4x32-10 call per (step j, candidate c, env
+ *    e, drone d): key = seed, counter = (low word of *tick, env_offset + e,
+ *    c · 32 + j, (4 << 24) | (i << 8) | d).  Word k gives u_k = ((x_k >> 8) + 1) ·
+ *    2^-24 in (0, 1]; z0, z1 = sqrt(-2 ln u0) · (cos, sin)(2π u1) and z2, z3
+ *    likewise from u2, u3 (float32): qs_mppi_sample's construction under domain
+ *    tag 4, with the iteration above the drone index.  candidates[j][0][e][d][a]
+ *    = mean[j][e][d][a] as it is; for c > 0, clamp(mean + std · z_a, lo, hi),
+ *    mean and std at [j][e][d][a], the sum left out (the mean copied) where that
+ *    std is 0.  The counter holds the global env id, so the noise does not depend
+ *    on how envs are sharded; iterations, ticks, envs, candidates, steps and
+ *    drones never share a counter.
+ *  - qs_cem_refit(p, i).  Per env e, in double: s_c = ret[c][e] -
+ *    (first_done[c][e] < n ? done_penalty : 0).  Candidates are ranked by the
+ *    total order "larger s first, lower c on equal s": -0.0 and 0.0 are equal,
+ *    -inf is a number, and a NaN ranks after every number, lower c first among
+ *    NaNs.  elites[r][e] = the candidate of rank r for r < K; iter_best[i][e] =
+ *    s of rank 0.  For every (j, d, a), with x_r = candidates[j][elites[r][e]][e]
+ *    [d][a]: m = (1/K) sum_r x_r and v = (1/K) sum_r (x_r - m)^2 (two passes,
+ *    population variance), in double and in a fixed order; mean = (float)((1 -
+ *    alpha) · m + alpha · (double)mean) and std = max((float)((1 - alpha) · sqrt(v) +
+ *    alpha · (double)std), sigma_min[a]); with alpha = 0 the old values are not
+ *    read.  Where sigma[a] = 0 the std is left as it is (0 after begin).  Two
+ *    launches.  It reads candidates, ret and first_done as they are: a caller
+ *    may fill them itself.
+ *  - qs_cem_finish.  action = mean[0]; mean[j] = mean[j + 1] for j < n - 1 and
+ *    mean[n - 1] holds; *tick += 1 (once a tick, not once an iteration).
+ *  - qs_cem_plan = begin, I × (sample(i), qs_score(h, n, C, candidates, NULL,
+ *    {ret, first_done}), refit(i)), finish.  QS_E_STATE before qs_reset, with
+ *    nothing launched.
+ *  - qs_cem_reset copies `mean` (device, [n][E][D][A]; NULL: zeros) into the
+ *    planner and sets *tick = 0.  A new planner is in that state with zeros.
+ *  - qs_cem_sample / qs_cem_refit with an iteration outside 0 .. I - 1:
+ *    QS_E_INVALID, nothing launched.
+ *  - qs_cem_create refusals (QS_E_INVALID, *out untouched): a handle with
+ *    qs_score_depth(h) = 0, horizon outside 1 .. qs_score_depth(h), candidates
+ *    < 2 or > 2^27, elites < 1, > candidates or > 1024, iterations outside
+ *    1 .. 16, lo >= hi or non-finite, a negative or non-finite sigma, sigma_min,
+ *    alpha or done_penalty, alpha >= 1, sigma_min[a] > sigma[a], and sizes beyond
+ *    the 32-bit offsets qs_score refuses.                                       */
+typedef struct qs_cem_spec {
+  int32_t horizon;      /* n: 1 .. qs_score_depth(h)                              */
+  int32_t candidates;   /* C >= 2; candidate 0 is the mean itself, unperturbed    */
+  int32_t elites;       /* K: 1 .. min(C, 1024)                                   */
+  int32_t iterations;   /* I: 1 .. 16                                             */
+  float sigma[4];       /* the spread every tick starts from, per action
+                           component (first A used), >= 0; 0: never perturbed     */
+  float sigma_min[4];   /* floor of the refitted spread, 0 <= sigma_min <= sigma  */
+  float lo, hi;         /* candidates are clipped to [lo, hi]; lo < hi            */
+  double alpha;         /* smoothing in [0, 1): the share of the old mean / std   */
+  double done_penalty;  /* subtracted from a candidate's score for env e when its
+                           first_done[c][e] < n                                   */
+  uint64_t seed;
+} qs_cem_spec;
+
+typedef struct qs_cem_bufs {  /* device pointers owned by the planner           */
+  float* mean;          /* [n][E][D][A]                                          */
+  float* std;           /* [n][E][D][A]                                          */
+  float* candidates;    /* [n][C][E][D][A]  (what qs_score reads)                */
+  double* ret;          /* [C][E]  qs_score's ret                                */
+  int32_t* first_done;  /* [C][E]                                                */
+  int32_t* elites;      /* [K][E]  the K best candidates of the last refit, in
+                           rank order                                            */
+  double* iter_best;    /* [I][E]  the best penalised score of each iteration    */
+  float* action;        /* [E][D][A] mean[0] as finish found it                  */
+  uint64_t* tick;       /* [1]     device counter, +1 per finish                 */
+} qs_cem_bufs;
+
+typedef struct qs_cem qs_cem;
+
+int qs_cem_create(qs_handle* h, const qs_cem_spec* spec, qs_cem** out);
+int qs_cem_destroy(qs_cem* p);
+int qs_cem_buffers(const qs_cem* p, qs_cem_bufs* out);
+int qs_cem_reset(qs_cem* p, const float* mean, void* stream);
+int qs_cem_begin(qs_cem* p, void* stream);
+int qs_cem_sample(qs_cem* p, int iteration, void* stream);
+int qs_cem_refit(qs_cem* p, int iteration, void* stream);
+int qs_cem_finish(qs_cem* p, void* stream);
+int qs_cem_plan(qs_cem* p, void* stream);
+
 /* Multi-step launches this handle has made so far (host, no device work):
  * out[0] on the general multi-step kernel instances, out[1] on the
  * shape-specialised one.  The specialised instance serves synthetic-policy

@@ -1,0 +1,618 @@
+// planner_cem.hip — the CEM planner tick on top of qs_score (include/quadswarm.h,
+// qs_cem_*; DESIGN.md §4a "CEM tick").
+//
+// A tick is begin, I × (sample, qs_score, refit), finish.  cem_sample_kernel is
+// mppi_sample_kernel (planner.hip) with a per-element spread and the iteration in
+// the Philox counter; cem_select_* ranks an env's candidates by their penalised
+// score and writes the K best in rank order; cem_refit_* fits a mean and a
+// standard deviation per (step, drone, component) to those K rows.  Everything
+// per env is summed in double in a fixed order (no float atomics; the select's
+// histogram uses integer LDS atomics, whose sums do not depend on their order),
+// the tick counter lives on the device, and nothing is read back, so a tick can
+// be captured and replayed.  The host arithmetic (sizes, variant, grids) is
+// cem_sizes.h.
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+#include <new>
+
+#include "quadswarm.h"
+#include "planner_link.h"
+#include "cem_sizes.h"
+#include "step_kernel.h"   // qs::philox
+
+namespace {
+
+#define CEM_HIP_TRY(expr)                                                                         \
+  do {                                                                                            \
+    hipError_t _e = (expr);                                                                       \
+    if (_e != hipSuccess) return qs::set_last_error(QS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+  } while (0)
+
+struct SampleParams {
+  const float* mean;         // [n][E][D][A]
+  const float* std;          // [n][E][D][A]
+  float* cand;               // [n][C][E][D][A]
+  const uint64_t* tick;
+  uint32_t k0, k1, genv0, iter;
+  int n, C, E, D, A;
+  float lo, hi;
+};
+
+struct SelectParams {
+  const double* ret;         // [C][E]
+  const int32_t* first_done; // [C][E]
+  int32_t* elites;           // [K][E]
+  double* iter_best;         // [E]: this iteration's row
+  double penalty;
+  int n, C, K, E;
+  int index_bytes;           // cem_index_bytes(C)
+};
+
+struct RefitParams {
+  const float* cand;         // [n][C][E][D][A]
+  const int32_t* elites;     // [K][E]
+  float* mean;               // [n][E][D][A]
+  float* std;                // [n][E][D][A]
+  double alpha;
+  int n, C, K, E, A, row, rowp;   // row = D · A, rowp = the power of two >= row
+  float sigma[4], sigma_min[4];
+};
+
+struct FillParams {
+  float* std;                // [n][E][D][A]
+  uint64_t total;            // n · E · D · A
+  int A;
+  float sigma[4];
+};
+
+struct FinishParams {
+  float* mean;               // [n][E][D][A]
+  float* action;             // [E][D][A]
+  uint64_t* tick;
+  uint64_t col;              // E · D · A
+  int n;
+};
+
+// 24-bit uniform in (0, 1]: ln u is finite.
+__device__ __forceinline__ float u01_open0(uint32_t x) { return (float)((x >> 8) + 1u) * (1.0f / 16777216.0f); }
+
+// ---- begin: the spread restarts at sigma ---------------------------------------
+__global__ __launch_bounds__(qs::kCemThreads) void cem_fill_kernel(FillParams P) {
+  const uint64_t t = (uint64_t)blockIdx.x * qs::kCemThreads + threadIdx.x;
+  if (t >= P.total) return;
+  P.std[t] = P.sigma[(int)(t % (uint64_t)P.A)];
+}
+
+// ---- sample: one thread per (candidate, env, drone) of step j = blockIdx.y ------
+// C · E · D is below 2^31 (cem_sizes.h), so the index arithmetic is 32-bit.  Only
+// the normals the action components use are formed.
+__global__ __launch_bounds__(qs::kCemThreads) void cem_sample_kernel(SampleParams P) {
+  const uint32_t v = blockIdx.x * (uint32_t)qs::kCemThreads + threadIdx.x;
+  const uint32_t ED = (uint32_t)P.E * (uint32_t)P.D, per_step = (uint32_t)P.C * ED;
+  if (v >= per_step) return;
+  const int j = blockIdx.y;
+  const uint32_t c = v / ED, ed = v - c * ED, e = ed / (uint32_t)P.D, d = ed - e * (uint32_t)P.D;
+  const size_t at = ((size_t)j * ED + ed) * P.A;
+  const float* mu = P.mean + at;
+  float* out = P.cand + ((size_t)j * per_step + v) * P.A;
+  if (c == 0) {
+    for (int a = 0; a < P.A; ++a) out[a] = mu[a];
+    return;
+  }
+  const float* sd = P.std + at;
+  const uint32_t tick = (uint32_t)*P.tick;
+  const qs::U4 x = qs::philox(qs::U4{tick, P.genv0 + e, c * 32u + (uint32_t)j,
+                                     ((uint32_t)qs::kCemTag << 24) | (P.iter << 8) | d},
+                              P.k0, P.k1);
+  const float two_pi = 6.283185307179586f;
+  float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  const float r0 = sqrtf(-2.0f * logf(u01_open0(x.x))), a0 = two_pi * u01_open0(x.y);
+  z[0] = r0 * cosf(a0);
+  if (P.A > 1) z[1] = r0 * sinf(a0);
+  if (P.A > 2) {   // (kernel-uniform)
+    const float r1 = sqrtf(-2.0f * logf(u01_open0(x.z))), a1 = two_pi * u01_open0(x.w);
+    z[2] = r1 * cosf(a1);
+    z[3] = r1 * sinf(a1);
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    if (a >= P.A) break;
+    const float sg = sd[a];
+    const float val = sg == 0.0f ? mu[a] : mu[a] + sg * z[a];
+    out[a] = fminf(fmaxf(val, P.lo), P.hi);
+  }
+}
+
+// ---- the order --------------------------------------------------------------------
+__device__ __forceinline__ double score_of(const SelectParams& P, size_t ce) {
+  return P.ret[ce] - (P.first_done[ce] < P.n ? P.penalty : 0.0);
+}
+// A score as an unsigned key that sorts as the total order wants: larger score,
+// larger key; -0.0 and 0.0 share one key; every NaN gets 0, below -inf's key.
+__device__ __forceinline__ uint64_t key_of(double s) {
+  if (s != s) return 0;
+  if (s == 0.0) s = 0.0;   // -0.0 -> 0.0
+  const uint64_t b = (uint64_t)__double_as_longlong(s);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+// Whether (k2, c2) comes before (k1, c1): the larger key, the lower c on a tie.
+__device__ __forceinline__ bool comes_before(uint64_t k2, int c2, uint64_t k1, int c1) {
+  return k2 > k1 || (k2 == k1 && c2 < c1);
+}
+
+// ---- select, one thread per env ------------------------------------------------
+// A candidate's rank is the number of candidates that come before it; the order
+// is total, so the ranks are 0 .. C - 1, each once.
+__global__ __launch_bounds__(qs::kCemThreads) void cem_select_thread_kernel(SelectParams P) {
+  const int e = blockIdx.x * qs::kCemThreads + threadIdx.x;
+  if (e >= P.E) return;
+  for (int c = 0; c < P.C; ++c) {
+    const double s = score_of(P, (size_t)c * P.E + e);
+    const uint64_t k = key_of(s);
+    int rank = 0;
+    for (int c2 = 0; c2 < P.C; ++c2) rank += comes_before(key_of(score_of(P, (size_t)c2 * P.E + e)), c2, k, c) ? 1 : 0;
+    if (rank < P.K) P.elites[(size_t)rank * P.E + e] = c;
+    if (rank == 0) P.iter_best[e] = s;
+  }
+}
+
+// ---- select, one workgroup per env -------------------------------------------------
+// The (key, C - 1 - c) pairs are distinct, so exactly K of them are >= the K-th
+// largest.  That pair is found a byte at a time from the top (8 passes over the
+// key, index_bytes over the index): a 256-bin histogram of the byte among the
+// candidates that match the bytes fixed so far, then wave 0 walks it from 255
+// down to the bin where the running count reaches what is still wanted.  The
+// passes end early once that bin holds exactly what is still wanted: whatever
+// matches the bytes fixed so far is then at or above the threshold.  The K
+// candidates at or above the threshold are gathered in LDS (in arrival order) and
+// ranked among themselves by counting, which puts them in the total order.
+__global__ __launch_bounds__(qs::kCemBlockThreads) void cem_select_block_kernel(SelectParams P) {
+  constexpr int kThreads = qs::kCemBlockThreads;
+  __shared__ uint64_t sh_key[qs::kCemStage];
+  __shared__ uint64_t sh_ek[qs::kCemMaxElites];
+  __shared__ int32_t sh_ec[qs::kCemMaxElites];
+  __shared__ uint32_t sh_hist[256];
+  __shared__ uint32_t sh_digit, sh_want, sh_done, sh_count;
+  const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int staged = P.C < qs::kCemStage ? P.C : qs::kCemStage;
+  for (int c = tid; c < staged; c += kThreads) sh_key[c] = key_of(score_of(P, (size_t)c * P.E + e));
+  if (tid == 0) sh_count = 0;
+  sh_ek[tid] = 0;   // (kCemMaxElites = kThreads slots; exactly K are filled below)
+  sh_ec[tid] = 0;
+  __syncthreads();
+  auto key_at = [&](int c) -> uint64_t { return c < staged ? sh_key[c] : key_of(score_of(P, (size_t)c * P.E + e)); };
+
+  uint64_t key_mask = 0, key_fix = 0;   // the bytes fixed so far, and their values
+  uint32_t idx_mask = 0, idx_fix = 0;
+  uint32_t want = (uint32_t)P.K;        // the threshold is the want-th largest among the matching
+  const int passes = 8 + P.index_bytes;
+  for (int pass = 0; pass < passes; ++pass) {
+    const bool in_key = pass < 8;
+    const int shift = in_key ? 56 - 8 * pass : 8 * (P.index_bytes - 1 - (pass - 8));
+    if (tid < 256) sh_hist[tid] = 0;
+    __syncthreads();
+    for (int base = 0; base < P.C; base += kThreads) {   // (a whole wave takes every trip: the ballots below)
+      const int c = base + tid;
+      bool active = false;
+      uint32_t digit = 0;
+      if (c < P.C) {
+        const uint64_t k = key_at(c);
+        const uint32_t ix = (uint32_t)(P.C - 1 - c);
+        if ((k & key_mask) == key_fix && (ix & idx_mask) == idx_fix) {
+          active = true;
+          digit = in_key ? (uint32_t)(k >> shift) & 255u : (ix >> shift) & 255u;
+        }
+      }
+      // scores of one magnitude share their top bytes: one add a wave where every lane names the same bin
+      const unsigned long long act = __ballot(active);
+      if (act != 0) {
+        const int first = __ffsll((long long)act) - 1;
+        const uint32_t d0 = (uint32_t)__shfl((int)digit, first, 64);
+        const unsigned long long same = __ballot(active && digit == d0);
+        if (same == act) {
+          if (lane == first) atomicAdd(&sh_hist[d0], (uint32_t)__popcll(act));
+        } else if (active) {
+          atomicAdd(&sh_hist[digit], 1u);
+        }
+      }
+    }
+    __syncthreads();
+    if (tid < 64) {   // wave 0: lane l holds bins 255 - 4l .. 252 - 4l, from the top
+      uint32_t h[4], own = 0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { h[q] = sh_hist[255 - 4 * lane - q]; own += h[q]; }
+      uint32_t incl = own;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)incl, off, 64);
+        if (lane >= off) incl += up;
+      }
+      uint32_t run = incl - own;
+      if (run < want && want <= incl) {   // one lane: the matching candidates are at least `want`
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          if (run < want && want <= run + h[q]) {
+            sh_digit = (uint32_t)(255 - 4 * lane - q);
+            sh_want = want - run;
+            sh_done = h[q] == want - run ? 1u : 0u;   // every candidate left in the bin is wanted
+          }
+          run += h[q];
+        }
+      }
+    }
+    __syncthreads();
+    const uint32_t g = sh_digit;
+    want = sh_want;
+    if (in_key) { key_mask |= 255ull << shift; key_fix |= (uint64_t)g << shift; }
+    else { idx_mask |= 255u << shift; idx_fix |= g << shift; }
+    if (sh_done) break;   // (the same word for every thread; written again two barriers on)
+  }
+  // the threshold pair, as far as its bytes were needed, is (key_fix, idx_fix): gather what is at or above it
+  for (int c = tid; c < P.C; c += kThreads) {
+    const uint64_t k = key_at(c), km = k & key_mask;
+    const uint32_t im = (uint32_t)(P.C - 1 - c) & idx_mask;
+    if (km > key_fix || (km == key_fix && im >= idx_fix)) {
+      const uint32_t slot = atomicAdd(&sh_count, 1u);
+      if (slot < (uint32_t)qs::kCemMaxElites) { sh_ek[slot] = k; sh_ec[slot] = c; }
+    }
+  }
+  __syncthreads();
+  if (tid < P.K) {
+    const uint64_t k = sh_ek[tid];
+    const int c = sh_ec[tid];
+    int rank = 0;
+#pragma unroll 8
+    for (int m = 0; m < P.K; ++m) rank += comes_before(sh_ek[m], sh_ec[m], k, c) ? 1 : 0;   // broadcast reads
+    P.elites[(size_t)rank * P.E + e] = c;
+    if (rank == 0) P.iter_best[e] = score_of(P, (size_t)c * P.E + e);
+  }
+}
+
+// ---- refit ------------------------------------------------------------------------
+__device__ __forceinline__ void store_fit(const RefitParams& P, int j, int e, int k, double m, double v) {
+  const size_t at = ((size_t)j * P.E + e) * P.row + k;
+  const int a = k % P.A;
+  float mu, sd;
+  if (P.alpha == 0.0) {   // the old values are not read
+    mu = (float)m;
+    sd = (float)sqrt(v);
+  } else {
+    mu = (float)((1.0 - P.alpha) * m + P.alpha * (double)P.mean[at]);
+    sd = (float)((1.0 - P.alpha) * sqrt(v) + P.alpha * (double)P.std[at]);
+  }
+  P.mean[at] = mu;
+  if (P.sigma[a] != 0.0f) P.std[at] = fmaxf(sd, P.sigma_min[a]);
+}
+
+// One thread per (j, e, d, a), looping over the K elites in rank order; the
+// threads of one env's row read one candidate row together.
+__global__ __launch_bounds__(qs::kCemThreads) void cem_refit_thread_kernel(RefitParams P) {
+  const uint64_t t = (uint64_t)blockIdx.x * qs::kCemThreads + threadIdx.x;
+  const size_t step = (size_t)P.E * P.row;
+  if (t >= (uint64_t)P.n * step) return;
+  const int j = (int)(t / step);
+  const size_t ek = t % step;
+  const int e = (int)(ek / P.row), k = (int)(ek % P.row);
+  const float* cj = P.cand + (size_t)j * P.C * step + ek;
+  double sum = 0.0;
+  for (int r = 0; r < P.K; ++r) sum += (double)cj[(size_t)P.elites[(size_t)r * P.E + e] * step];
+  const double m = sum / (double)P.K;
+  double sq = 0.0;
+  for (int r = 0; r < P.K; ++r) {
+    const double d = (double)cj[(size_t)P.elites[(size_t)r * P.E + e] * step] - m;
+    sq += d * d;
+  }
+  store_fit(P, j, e, k, m, sq / (double)P.K);
+}
+
+// The sum over the whole workgroup of `acc` per component k = tid mod rowp, handed
+// to every thread.  rowp is a power of two, so the lanes of one component sit
+// rowp apart in a wave: an xor tree over the offsets 32 .. rowp sums them, then
+// the partials (one per wave, or one per group where a row spans whole waves)
+// meet in an LDS tree, as in mppi_sum_block_kernel.
+__device__ __forceinline__ double block_row_sum(double acc, double* part, int tid, int rowp) {
+  const int lane = tid & 63, wave = tid >> 6;
+  int parts;
+  if (rowp <= 64) {
+    for (int off = 32; off >= rowp; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    parts = qs::kCemBlockThreads / 64;
+    if (lane < rowp) part[wave * rowp + lane] = acc;
+  } else {
+    parts = qs::kCemBlockThreads / rowp;
+    part[tid] = acc;   // = part[g * rowp + k]
+  }
+  __syncthreads();
+  for (int s = parts >> 1; s >= 1; s >>= 1) {
+    if (tid < s * rowp) part[tid] += part[tid + s * rowp];
+    __syncthreads();
+  }
+  const double total = part[tid & (rowp - 1)];
+  __syncthreads();   // part is used again
+  return total;
+}
+
+// One workgroup per (env, step): thread t holds component k = t mod rowp of elite
+// group g = t / rowp and strides over the ranks by the group count.
+__global__ __launch_bounds__(qs::kCemBlockThreads) void cem_refit_block_kernel(RefitParams P) {
+  __shared__ double part[qs::kCemBlockThreads];
+  __shared__ int32_t sh_el[qs::kCemMaxElites];
+  const int e = blockIdx.x % P.E, j = blockIdx.x / P.E, tid = threadIdx.x;
+  if (tid < P.K) sh_el[tid] = P.elites[(size_t)tid * P.E + e];
+  __syncthreads();
+  const int rowp = P.rowp, k = tid & (rowp - 1), g = tid / rowp, G = qs::kCemBlockThreads / rowp;
+  const size_t step = (size_t)P.E * P.row;
+  const float* cj = P.cand + (size_t)j * P.C * step + (size_t)e * P.row;
+  double acc = 0.0;
+  if (k < P.row) {
+#pragma unroll 4
+    for (int r = g; r < P.K; r += G) acc += (double)cj[(size_t)sh_el[r] * step + k];
+  }
+  const double m = block_row_sum(acc, part, tid, rowp) / (double)P.K;
+  acc = 0.0;
+  if (k < P.row) {
+#pragma unroll 4
+    for (int r = g; r < P.K; r += G) {
+      const double d = (double)cj[(size_t)sh_el[r] * step + k] - m;
+      acc += d * d;
+    }
+  }
+  const double v = block_row_sum(acc, part, tid, rowp) / (double)P.K;
+  if (tid < P.row) store_fit(P, j, e, tid, m, v);
+}
+
+// ---- finish: one thread per (e, d, a) column walks the steps upward, so nobody
+// reads a step another thread has overwritten -------------------------------------
+__global__ __launch_bounds__(qs::kCemThreads) void cem_finish_kernel(FinishParams P) {
+  const uint64_t t = (uint64_t)blockIdx.x * qs::kCemThreads + threadIdx.x;
+  if (t == 0) *P.tick += 1;
+  if (t >= P.col) return;
+  float cur = P.mean[t];
+  P.action[t] = cur;
+  for (int j = 0; j + 1 < P.n; ++j) {
+    cur = P.mean[(size_t)(j + 1) * P.col + t];
+    P.mean[(size_t)j * P.col + t] = cur;
+  }
+}
+
+}  // namespace
+
+struct qs_cem {
+  qs_handle* h = nullptr;
+  qs_cem_spec spec;
+  qs::HandleInfo info;
+  qs::CemShape shape;
+  qs::CemVariant variant;
+  qs::CemGrids grids;
+  uint64_t bytes[qs::kCemBufs];
+  void* buf[qs::kCemBufs];
+  std::vector<const float*> steps;   // candidates' n step pointers, the host array qs_score reads
+};
+
+namespace {
+
+int begin_impl(qs_cem* p, hipStream_t st) {
+  FillParams P;
+  P.std = (float*)p->buf[qs::kCemStd];
+  P.total = p->bytes[qs::kCemStd] / 4u;
+  P.A = (int)p->shape.A;
+  for (int a = 0; a < 4; ++a) P.sigma[a] = p->spec.sigma[a];
+  hipLaunchKernelGGL(cem_fill_kernel, dim3(p->grids.fill), dim3(qs::kCemThreads), 0, st, P);
+  CEM_HIP_TRY(hipGetLastError());
+  return QS_OK;
+}
+
+int sample_impl(qs_cem* p, int iteration, hipStream_t st) {
+  SampleParams P;
+  P.mean = (const float*)p->buf[qs::kCemMean];
+  P.std = (const float*)p->buf[qs::kCemStd];
+  P.cand = (float*)p->buf[qs::kCemCandidates];
+  P.tick = (const uint64_t*)p->buf[qs::kCemTick];
+  P.k0 = (uint32_t)p->spec.seed; P.k1 = (uint32_t)(p->spec.seed >> 32);
+  P.genv0 = (uint32_t)p->info.env_offset;
+  P.iter = (uint32_t)iteration;
+  P.n = (int)p->shape.n; P.C = (int)p->shape.C; P.E = (int)p->shape.E; P.D = (int)p->shape.D; P.A = (int)p->shape.A;
+  P.lo = p->spec.lo; P.hi = p->spec.hi;
+  hipLaunchKernelGGL(cem_sample_kernel, dim3(p->grids.sample, (uint32_t)p->shape.n), dim3(qs::kCemThreads), 0, st, P);
+  CEM_HIP_TRY(hipGetLastError());
+  return QS_OK;
+}
+
+int refit_impl(qs_cem* p, int iteration, hipStream_t st) {
+  SelectParams S;
+  S.ret = (const double*)p->buf[qs::kCemRet];
+  S.first_done = (const int32_t*)p->buf[qs::kCemFirstDone];
+  S.elites = (int32_t*)p->buf[qs::kCemElites];
+  S.iter_best = (double*)p->buf[qs::kCemIterBest] + (size_t)iteration * (size_t)p->shape.E;
+  S.penalty = p->spec.done_penalty;
+  S.n = (int)p->shape.n; S.C = (int)p->shape.C; S.K = (int)p->shape.K; S.E = (int)p->shape.E;
+  S.index_bytes = qs::cem_index_bytes(p->shape.C);
+  RefitParams R;
+  R.cand = (const float*)p->buf[qs::kCemCandidates];
+  R.elites = (const int32_t*)p->buf[qs::kCemElites];
+  R.mean = (float*)p->buf[qs::kCemMean];
+  R.std = (float*)p->buf[qs::kCemStd];
+  R.alpha = p->spec.alpha;
+  R.n = S.n; R.C = S.C; R.K = S.K; R.E = S.E; R.A = (int)p->shape.A;
+  R.row = (int)(p->shape.D * p->shape.A);
+  R.rowp = qs::mppi_row_pow2(R.row);
+  for (int a = 0; a < 4; ++a) { R.sigma[a] = p->spec.sigma[a]; R.sigma_min[a] = p->spec.sigma_min[a]; }
+  if (p->variant == qs::kCemPerBlock) {
+    hipLaunchKernelGGL(cem_select_block_kernel, dim3(p->grids.select), dim3(qs::kCemBlockThreads), 0, st, S);
+    CEM_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cem_refit_block_kernel, dim3(p->grids.refit), dim3(qs::kCemBlockThreads), 0, st, R);
+  } else {
+    hipLaunchKernelGGL(cem_select_thread_kernel, dim3(p->grids.select), dim3(qs::kCemThreads), 0, st, S);
+    CEM_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cem_refit_thread_kernel, dim3(p->grids.refit), dim3(qs::kCemThreads), 0, st, R);
+  }
+  CEM_HIP_TRY(hipGetLastError());
+  return QS_OK;
+}
+
+int finish_impl(qs_cem* p, hipStream_t st) {
+  FinishParams P;
+  P.mean = (float*)p->buf[qs::kCemMean];
+  P.action = (float*)p->buf[qs::kCemAction];
+  P.tick = (uint64_t*)p->buf[qs::kCemTick];
+  P.col = p->bytes[qs::kCemAction] / 4u;
+  P.n = (int)p->shape.n;
+  hipLaunchKernelGGL(cem_finish_kernel, dim3(p->grids.finish), dim3(qs::kCemThreads), 0, st, P);
+  CEM_HIP_TRY(hipGetLastError());
+  return QS_OK;
+}
+
+int bad_iteration(const qs_cem* p, int iteration, const char* who) {
+  return qs::set_last_error(QS_E_INVALID, std::string(who) + ": iteration = " + std::to_string(iteration) +
+                                              " is outside 0 .. iterations - 1 = " + std::to_string(p->spec.iterations - 1));
+}
+
+void free_bufs(qs_cem* p) {
+  for (void* b : p->buf)
+    if (b) (void)hipFree(b);
+}
+
+}  // namespace
+
+extern "C" {
+
+int qs_cem_create(qs_handle* h, const qs_cem_spec* spec, qs_cem** out) {
+  using qs::set_last_error;
+  if (!h || !spec || !out) return set_last_error(QS_E_INVALID, "qs_cem_create: null argument");
+  const int depth = qs_score_depth(h);
+  if (depth < 1)
+    return set_last_error(QS_E_INVALID, "qs_cem_create: this handle cannot score (qs_score_depth = 0): a layout whose "
+                                        "reset draws can be rejected, or a Flock / Meetup / LeaderFollower task");
+  if (spec->horizon < 1 || spec->horizon > depth)
+    return set_last_error(QS_E_INVALID, "qs_cem_create: horizon = " + std::to_string(spec->horizon) +
+                                            " is outside 1 .. qs_score_depth = " + std::to_string(depth));
+  if (spec->candidates < 2)
+    return set_last_error(QS_E_INVALID, "qs_cem_create: candidates must be >= 2 (candidate 0 is the mean itself)");
+  if (spec->elites < 1 || spec->elites > spec->candidates || spec->elites > qs::kCemMaxElites)
+    return set_last_error(QS_E_INVALID, "qs_cem_create: elites = " + std::to_string(spec->elites) +
+                                            " is outside 1 .. min(candidates, " + std::to_string(qs::kCemMaxElites) + ")");
+  if (spec->iterations < 1 || spec->iterations > qs::kCemMaxIterations)
+    return set_last_error(QS_E_INVALID, "qs_cem_create: iterations = " + std::to_string(spec->iterations) +
+                                            " is outside 1 .. " + std::to_string(qs::kCemMaxIterations));
+  if (!(spec->lo < spec->hi) || !std::isfinite(spec->lo) || !std::isfinite(spec->hi))
+    return set_last_error(QS_E_INVALID, "qs_cem_create: lo must be below hi, both finite");
+  qs_dims d;
+  if (int rc = qs_get_dims(h, &d)) return rc;
+  for (int a = 0; a < d.act_dim && a < 4; ++a) {
+    if (!(spec->sigma[a] >= 0.0f) || !std::isfinite(spec->sigma[a]))
+      return set_last_error(QS_E_INVALID, "qs_cem_create: sigma[" + std::to_string(a) + "] must be finite and >= 0");
+    if (!(spec->sigma_min[a] >= 0.0f) || !std::isfinite(spec->sigma_min[a]))
+      return set_last_error(QS_E_INVALID, "qs_cem_create: sigma_min[" + std::to_string(a) + "] must be finite and >= 0");
+    if (spec->sigma_min[a] > spec->sigma[a])
+      return set_last_error(QS_E_INVALID, "qs_cem_create: sigma_min[" + std::to_string(a) + "] is above sigma[" +
+                                              std::to_string(a) + "]");
+  }
+  if (!(spec->alpha >= 0.0) || !(spec->alpha < 1.0))
+    return set_last_error(QS_E_INVALID, "qs_cem_create: alpha must be in [0, 1)");
+  if (!(spec->done_penalty >= 0.0) || !std::isfinite(spec->done_penalty))
+    return set_last_error(QS_E_INVALID, "qs_cem_create: done_penalty must be finite and >= 0");
+  qs_cem* p = new (std::nothrow) qs_cem;
+  if (!p) return set_last_error(QS_E_NOMEM, "qs_cem_create: out of host memory");
+  p->h = h;
+  p->spec = *spec;
+  qs::handle_info(h, &p->info);
+  p->shape = qs::CemShape{spec->horizon, spec->candidates, spec->elites, spec->iterations, d.num_envs, d.num_drones, d.act_dim};
+  for (void*& b : p->buf) b = nullptr;
+  if (!qs::cem_sizes(p->shape, p->bytes)) {
+    delete p;
+    return set_last_error(QS_E_INVALID, "qs_cem_create: candidates * num_envs * num_drones is too large (the 32-bit "
+                                        "offsets of qs_score, at most 2^27 candidates)");
+  }
+  p->variant = qs::cem_variant(p->shape.E, p->shape.C, p->shape.D * p->shape.A);
+  p->grids = qs::cem_grids(p->shape, p->variant);
+  hipError_t e = hipSetDevice(p->info.device);
+  for (int i = 0; i < qs::kCemBufs && e == hipSuccess; ++i) {
+    e = hipMalloc(&p->buf[i], p->bytes[i]);
+    if (e == hipSuccess) e = hipMemset(p->buf[i], 0, p->bytes[i]);
+  }
+  if (e != hipSuccess) {
+    free_bufs(p);
+    delete p;
+    return set_last_error(e == hipErrorOutOfMemory ? QS_E_NOMEM : QS_E_HIP,
+                          std::string("qs_cem_create: ") + hipGetErrorString(e));
+  }
+  const size_t step = (size_t)(p->bytes[qs::kCemCandidates] / 4u / (uint64_t)p->shape.n);
+  for (int j = 0; j < p->shape.n; ++j) p->steps.push_back((const float*)p->buf[qs::kCemCandidates] + (size_t)j * step);
+  *out = p;
+  return QS_OK;
+}
+
+int qs_cem_destroy(qs_cem* p) {
+  if (!p) return QS_OK;
+  (void)hipSetDevice(p->info.device);   // teardown: best effort
+  free_bufs(p);
+  delete p;
+  return QS_OK;
+}
+
+int qs_cem_buffers(const qs_cem* p, qs_cem_bufs* out) {
+  if (!p || !out) return qs::set_last_error(QS_E_INVALID, "qs_cem_buffers: null argument");
+  out->mean = (float*)p->buf[qs::kCemMean];
+  out->std = (float*)p->buf[qs::kCemStd];
+  out->candidates = (float*)p->buf[qs::kCemCandidates];
+  out->ret = (double*)p->buf[qs::kCemRet];
+  out->first_done = (int32_t*)p->buf[qs::kCemFirstDone];
+  out->elites = (int32_t*)p->buf[qs::kCemElites];
+  out->iter_best = (double*)p->buf[qs::kCemIterBest];
+  out->action = (float*)p->buf[qs::kCemAction];
+  out->tick = (uint64_t*)p->buf[qs::kCemTick];
+  return QS_OK;
+}
+
+int qs_cem_reset(qs_cem* p, const float* mean, void* stream) {
+  if (!p) return qs::set_last_error(QS_E_INVALID, "qs_cem_reset: null planner");
+  hipStream_t st = (hipStream_t)stream;
+  CEM_HIP_TRY(hipSetDevice(p->info.device));
+  if (mean)
+    CEM_HIP_TRY(hipMemcpyAsync(p->buf[qs::kCemMean], mean, p->bytes[qs::kCemMean], hipMemcpyDeviceToDevice, st));
+  else
+    CEM_HIP_TRY(hipMemsetAsync(p->buf[qs::kCemMean], 0, p->bytes[qs::kCemMean], st));
+  CEM_HIP_TRY(hipMemsetAsync(p->buf[qs::kCemTick], 0, p->bytes[qs::kCemTick], st));
+  return QS_OK;
+}
+
+int qs_cem_begin(qs_cem* p, void* stream) {
+  if (!p) return qs::set_last_error(QS_E_INVALID, "qs_cem_begin: null planner");
+  return begin_impl(p, (hipStream_t)stream);
+}
+
+int qs_cem_sample(qs_cem* p, int iteration, void* stream) {
+  if (!p) return qs::set_last_error(QS_E_INVALID, "qs_cem_sample: null planner");
+  if (iteration < 0 || iteration >= p->spec.iterations) return bad_iteration(p, iteration, "qs_cem_sample");
+  return sample_impl(p, iteration, (hipStream_t)stream);
+}
+
+int qs_cem_refit(qs_cem* p, int iteration, void* stream) {
+  if (!p) return qs::set_last_error(QS_E_INVALID, "qs_cem_refit: null planner");
+  if (iteration < 0 || iteration >= p->spec.iterations) return bad_iteration(p, iteration, "qs_cem_refit");
+  return refit_impl(p, iteration, (hipStream_t)stream);
+}
+
+int qs_cem_finish(qs_cem* p, void* stream) {
+  if (!p) return qs::set_last_error(QS_E_INVALID, "qs_cem_finish: null planner");
+  return finish_impl(p, (hipStream_t)stream);
+}
+
+int qs_cem_plan(qs_cem* p, void* stream) {
+  if (!p) return qs::set_last_error(QS_E_INVALID, "qs_cem_plan: null planner");
+  qs::handle_info(p->h, &p->info);
+  if (!p->info.reset_done) return qs::set_last_error(QS_E_STATE, "qs_cem_plan: call qs_reset first");
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = begin_impl(p, st)) return rc;
+  const qs_score_out so{p->buf[qs::kCemRet], (int32_t*)p->buf[qs::kCemFirstDone]};
+  for (int i = 0; i < p->spec.iterations; ++i) {
+    if (int rc = sample_impl(p, i, st)) return rc;
+    if (int rc = qs_score(p->h, (int)p->shape.n, (int)p->shape.C, p->steps.data(), nullptr, &so, stream)) return rc;
+    if (int rc = refit_impl(p, i, st)) return rc;
+  }
+  return finish_impl(p, st);
+}
+
+}  // extern "C"

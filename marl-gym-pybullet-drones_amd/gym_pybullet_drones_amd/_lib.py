@@ -74,6 +74,21 @@ class QsMppiBufs(ctypes.Structure):
                 ("action", ctypes.c_void_p), ("tick", ctypes.c_void_p)]
 
 
+class QsCemSpec(ctypes.Structure):
+    """include/quadswarm.h qs_cem_spec: what a CEM planner is created from."""
+    _fields_ = [("horizon", ctypes.c_int32), ("candidates", ctypes.c_int32), ("elites", ctypes.c_int32),
+                ("iterations", ctypes.c_int32), ("sigma", ctypes.c_float * 4), ("sigma_min", ctypes.c_float * 4),
+                ("lo", ctypes.c_float), ("hi", ctypes.c_float), ("alpha", ctypes.c_double),
+                ("done_penalty", ctypes.c_double), ("seed", ctypes.c_uint64)]
+
+
+class QsCemBufs(ctypes.Structure):
+    """include/quadswarm.h qs_cem_bufs: the CEM planner's device buffers."""
+    _fields_ = [("mean", ctypes.c_void_p), ("std", ctypes.c_void_p), ("candidates", ctypes.c_void_p),
+                ("ret", ctypes.c_void_p), ("first_done", ctypes.c_void_p), ("elites", ctypes.c_void_p),
+                ("iter_best", ctypes.c_void_p), ("action", ctypes.c_void_p), ("tick", ctypes.c_void_p)]
+
+
 EPISODE_DTYPE = np.dtype([("ret", "<f8"), ("len", "<i4"), ("env", "<i4"), ("seq", "<i8")])
 
 # Every symbol include/quadswarm.h declares (tests check the .so exports them).
@@ -81,7 +96,8 @@ ABI_VERSION = 4   # include/quadswarm.h QS_ABI_VERSION
 EXPORTS = ("qs_create", "qs_destroy", "qs_last_error", "qs_abi_version", "qs_get_dims", "qs_reset",
            "qs_reset_envs", "qs_step", "qs_step_many", "qs_step_seq", "qs_score_depth", "qs_score",
            "qs_mppi_create", "qs_mppi_destroy", "qs_mppi_buffers", "qs_mppi_reset", "qs_mppi_sample", "qs_mppi_update",
-           "qs_mppi_plan", "qs_launch_counts", "qs_ring_counts", "qs_state_io", "qs_episode_log", "qs_reset_error", "qs_calib_copy",
+           "qs_mppi_plan", "qs_cem_create", "qs_cem_destroy", "qs_cem_buffers", "qs_cem_reset", "qs_cem_begin", "qs_cem_sample",
+           "qs_cem_refit", "qs_cem_finish", "qs_cem_plan", "qs_launch_counts", "qs_ring_counts", "qs_state_io", "qs_episode_log", "qs_reset_error", "qs_calib_copy",
            # include/qs_learner.h
            "qs_gae", "qs_adam_gated", "qs_adam_commit", "qs_ppo_heads", "qs_ppo_heads_work_bytes",
            "qs_mlp_bias_tanh", "qs_mlp_bwd_blocks", "qs_mlp_tanh_bwd", "qs_mlp_sum_partials",
@@ -154,6 +170,16 @@ def load():
         L.qs_mppi_sample.argtypes = [vp, vp]
         L.qs_mppi_update.argtypes = [vp, vp]
         L.qs_mppi_plan.argtypes = [vp, vp]
+    if hasattr(L, "qs_cem_create"):   # (a QS_DEV_LIB build from before the entry points: A/B runs)
+        L.qs_cem_create.argtypes = [vp, ctypes.POINTER(QsCemSpec), ctypes.POINTER(vp)]
+        L.qs_cem_destroy.argtypes = [vp]
+        L.qs_cem_buffers.argtypes = [vp, ctypes.POINTER(QsCemBufs)]
+        L.qs_cem_reset.argtypes = [vp, vp, vp]
+        L.qs_cem_begin.argtypes = [vp, vp]
+        L.qs_cem_sample.argtypes = [vp, i32, vp]
+        L.qs_cem_refit.argtypes = [vp, i32, vp]
+        L.qs_cem_finish.argtypes = [vp, vp]
+        L.qs_cem_plan.argtypes = [vp, vp]
     if hasattr(L, "qs_launch_counts"):   # (a QS_DEV_LIB build from before the entry point: A/B runs)
         L.qs_launch_counts.argtypes = [vp, ctypes.POINTER(i64)]
     if hasattr(L, "qs_ring_counts"):
@@ -224,7 +250,7 @@ def load():
     L.qs_rms_update.argtypes = [i64, ctypes.c_int32] + [vp] * 7
     L.qs_rms_normalize.argtypes = [i64, ctypes.c_int32, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp]
     for name in EXPORTS:
-        if (name in ("qs_launch_counts", "qs_ring_counts", "qs_score_depth", "qs_score") or name.startswith("qs_mppi_")) and not hasattr(L, name):
+        if (name in ("qs_launch_counts", "qs_ring_counts", "qs_score_depth", "qs_score") or name.startswith(("qs_mppi_", "qs_cem_"))) and not hasattr(L, name):
             continue   # (a QS_DEV_LIB build from before the entry point)
         if name not in ("qs_last_error", "qs_learner_last_error", "qs_rms_last_error", "qs_ppo_small_last_error",
                         "qs_rollout_last_error"):

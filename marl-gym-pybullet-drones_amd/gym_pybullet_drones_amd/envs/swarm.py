@@ -348,6 +348,20 @@ class QuadSwarm:
         self.__dict__.setdefault("_planners", weakref.WeakSet()).add(planner)   # close() ends them first
         return planner
 
+    def cem(self, horizon, candidates, elites, sigma, iterations=3, lo=-1.0, hi=1.0, alpha=0.0, sigma_min=0.0,
+            done_penalty=0.0, seed=0):
+        """A `CEMPlanner` on this swarm (qs_cem_create): per tick and env,
+        `iterations` rounds of drawing `candidates` action sequences of `horizon`
+        steps (1 .. score_depth()) round a mean with a per-element spread (started
+        from `sigma` at every tick: a number or one per action component), clipped
+        to [lo, hi], scoring them from the swarm's current state and refitting mean
+        and spread to the `elites` best, smoothed by `alpha` and floored at
+        `sigma_min`; `done_penalty` is taken off a candidate that ends an episode."""
+        planner = CEMPlanner(self, horizon, candidates, elites, sigma, iterations, lo, hi, alpha, sigma_min,
+                             done_penalty, seed)
+        self.__dict__.setdefault("_planners", weakref.WeakSet()).add(planner)   # close() ends them first
+        return planner
+
     def launch_counts(self):
         """(general, hot): the multi-step launches made so far on the general kernel
         instances and on the shape-specialised one (qs_launch_counts; QS_HOT_SHAPE=0
@@ -501,6 +515,117 @@ class MPPIPlanner:
         if getattr(self, "_p", None):
             torch.cuda.synchronize(self.swarm.device)
             self.lib.qs_mppi_destroy(self._p)
+            self._p = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CEMPlanner:
+    """The native CEM tick round `QuadSwarm.score` (qs_cem_*, include/quadswarm.h).
+
+    `begin()` restarts the spread `std` at sigma; `sample(i)` draws `candidates`
+    sequences round `mean` with spread `std` (candidate 0 is the mean itself);
+    `refit(i)` ranks them by the scores in `ret` / `first_done`, writes the
+    `elites` best in rank order and refits `mean` and `std` to them; `finish()`
+    takes `mean[0]` as `action` and shifts the mean by one step.  `plan()` is
+    begin, `iterations` times (sample, score from the swarm's current state,
+    refit), finish.  Every call is a few launches on the current stream with no
+    host sync, and may be captured into a graph together with the `step` that
+    runs `action`: the tick counter that keys the noise lives on the device.
+
+    The buffers are torch tensors that view the planner's device memory (no
+    copies; they dangle after `close()`): mean and std (n, E, D, A), candidates
+    (n, C, E, D, A), ret (C, E) float64, first_done (C, E) int32, elites (K, E)
+    int32, iter_best (I, E) float64, action (E, D, A), tick (1,) (the uint64
+    counter, viewed as int64).  The swarm must outlive the planner."""
+
+    def __init__(self, swarm, horizon, candidates, elites, sigma, iterations=3, lo=-1.0, hi=1.0, alpha=0.0,
+                 sigma_min=0.0, done_penalty=0.0, seed=0):
+        self.swarm, self.lib = swarm, swarm.lib
+        if not hasattr(self.lib, "qs_cem_create"):
+            raise L.QuadSwarmError(f"{L.LIB_PATH} has no qs_cem_create: rebuild the HIP extension")
+        A = swarm.act_dim
+
+        def per_component(v, what):
+            out = [float(v)] * A if np.isscalar(v) else [float(s) for s in v]
+            if len(out) != A:
+                raise ValueError(f"{what} must be a number or one per action component ({A})")
+            return out
+
+        sig, smin = per_component(sigma, "sigma"), per_component(sigma_min, "sigma_min")
+        spec = L.QsCemSpec()
+        spec.horizon, spec.candidates, spec.elites, spec.iterations = int(horizon), int(candidates), int(elites), int(iterations)
+        for a in range(A):
+            spec.sigma[a], spec.sigma_min[a] = sig[a], smin[a]
+        spec.lo, spec.hi, spec.alpha, spec.done_penalty = float(lo), float(hi), float(alpha), float(done_penalty)
+        spec.seed = int(seed)
+        self.spec = spec
+        self.horizon, self.num_candidates, self.num_elites, self.iterations = (int(horizon), int(candidates), int(elites),
+                                                                               int(iterations))
+        self._p = ctypes.c_void_p()
+        self._stepper = swarm.step   # what step_t runs the action with (SwarmVecEnv.cem: its step_t)
+        with torch.cuda.device(swarm.device):
+            L.check(self.lib.qs_cem_create(swarm._h, ctypes.byref(spec), ctypes.byref(self._p)), "qs_cem_create")
+        bufs = L.QsCemBufs()
+        L.check(self.lib.qs_cem_buffers(self._p, ctypes.byref(bufs)), "qs_cem_buffers")
+        n, C, K, I, E, D = self.horizon, self.num_candidates, self.num_elites, self.iterations, swarm.num_envs, swarm.num_drones
+
+        def view(ptr, shape, typestr):
+            return torch.as_tensor(_DeviceSpan(ptr, shape, typestr), device=swarm.device)
+
+        self.mean = view(bufs.mean, (n, E, D, A), "<f4")
+        self.std = view(bufs.std, (n, E, D, A), "<f4")
+        self.candidates = view(bufs.candidates, (n, C, E, D, A), "<f4")
+        self.ret = view(bufs.ret, (C, E), "<f8")
+        self.first_done = view(bufs.first_done, (C, E), "<i4")
+        self.elites = view(bufs.elites, (K, E), "<i4")
+        self.iter_best = view(bufs.iter_best, (I, E), "<f8")
+        self.action = view(bufs.action, (E, D, A), "<f4")
+        self.tick = view(bufs.tick, (1,), "<i8")
+
+    def _stream(self):
+        return self.swarm._stream()
+
+    def reset(self, mean=None):
+        """Set the mean sequence ((n, E, D, A) float32 on the device; None: zeros) and tick = 0."""
+        if mean is not None:
+            if (not isinstance(mean, torch.Tensor) or mean.dtype != torch.float32 or not mean.is_contiguous()
+                    or mean.device != self.swarm.device or tuple(mean.shape) != tuple(self.mean.shape)):
+                raise ValueError(f"mean must be a contiguous float32 {tuple(self.mean.shape)} tensor on "
+                                 f"{self.swarm.device}")
+        L.check(self.lib.qs_cem_reset(self._p, L.ptr(mean), self._stream()), "qs_cem_reset")
+
+    def begin(self):
+        L.check(self.lib.qs_cem_begin(self._p, self._stream()), "qs_cem_begin")
+
+    def sample(self, iteration=0):
+        L.check(self.lib.qs_cem_sample(self._p, int(iteration), self._stream()), "qs_cem_sample")
+
+    def refit(self, iteration=0):
+        L.check(self.lib.qs_cem_refit(self._p, int(iteration), self._stream()), "qs_cem_refit")
+
+    def finish(self):
+        L.check(self.lib.qs_cem_finish(self._p, self._stream()), "qs_cem_finish")
+
+    def plan(self):
+        """One planner tick from the swarm's current state; returns `action`."""
+        L.check(self.lib.qs_cem_plan(self._p, self._stream()), "qs_cem_plan")
+        return self.action
+
+    def step_t(self, **bufs):
+        """One receding-horizon tick: `plan()`, then the control step that runs
+        `action` (the swarm's `step`, or `SwarmVecEnv.step_t`), with its return."""
+        self.plan()
+        return self._stepper(self.action, **bufs)
+
+    def close(self):
+        if getattr(self, "_p", None):
+            torch.cuda.synchronize(self.swarm.device)
+            self.lib.qs_cem_destroy(self._p)
             self._p = ctypes.c_void_p()
 
     def __del__(self):
