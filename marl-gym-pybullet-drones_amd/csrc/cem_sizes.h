@@ -17,8 +17,8 @@
 namespace qs {
 
 constexpr int kCemTag = 4;               // Philox domain tag of the CEM noise (3: the MPPI planner's)
-constexpr int kCemThreads = 256;         // workgroup of begin, sample, finish and the per-thread variants
-constexpr int kCemBlockThreads = 1024;   // workgroup of the per-workgroup select and refit (16 waves)
+constexpr int kCemThreads = kPlannerThreads;             // begin, sample, finish and the per-thread variants
+constexpr int kCemBlockThreads = kPlannerBlockThreads;   // the per-workgroup select and refit
 constexpr int kCemMaxElites = 1024;      // K at most: one elite per thread of the select workgroup
 constexpr int kCemMaxIterations = 16;    // I at most (the counter word gives the iteration bits 8 .. 15)
 constexpr int kCemStage = 4096;          // sort keys the per-workgroup select keeps in LDS (32 KB); the keys of

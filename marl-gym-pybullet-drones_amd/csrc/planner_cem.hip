@@ -1,9 +1,10 @@
 // planner_cem.hip — the CEM planner tick on top of qs_score (include/quadswarm.h,
 // qs_cem_*; DESIGN.md §4a "CEM tick").
 //
-// A tick is begin, I × (sample, qs_score, refit), finish.  cem_sample_kernel is
-// mppi_sample_kernel (planner.hip) with a per-element spread and the iteration in
-// the Philox counter; cem_select_* ranks an env's candidates by their penalised
+// A tick is begin, I × (sample, qs_score, refit), finish.  The sample is
+// planner_sample_kernel (shared with the MPPI tick, planner_common.h) with a
+// per-element spread and the iteration in the Philox counter; cem_select_* ranks
+// an env's candidates by their penalised
 // score and writes the K best in rank order; cem_refit_* fits a mean and a
 // standard deviation per (step, drone, component) to those K rows.  Everything
 // per env is summed in double in a fixed order (no float atomics; the select's
@@ -11,34 +12,15 @@
 // the tick counter lives on the device, and nothing is read back, so a tick can
 // be captured and replayed.  The host arithmetic (sizes, variant, grids) is
 // cem_sizes.h.
-#include <hip/hip_runtime.h>
-#include <cmath>
-#include <cstdint>
-#include <string>
-#include <vector>
-#include <new>
-
-#include "quadswarm.h"
-#include "planner_link.h"
+#include "planner_common.h"
 #include "cem_sizes.h"
-#include "step_kernel.h"   // qs::philox
 
 namespace {
 
-#define CEM_HIP_TRY(expr)                                                                         \
-  do {                                                                                            \
-    hipError_t _e = (expr);                                                                       \
-    if (_e != hipSuccess) return qs::set_last_error(QS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-struct SampleParams {
-  const float* mean;         // [n][E][D][A]
+// The spread of an element, from memory.
+struct StdMem {
   const float* std;          // [n][E][D][A]
-  float* cand;               // [n][C][E][D][A]
-  const uint64_t* tick;
-  uint32_t k0, k1, genv0, iter;
-  int n, C, E, D, A;
-  float lo, hi;
+  __device__ __forceinline__ float at(size_t i, int a) const { return std[i + a]; }
 };
 
 struct SelectParams {
@@ -76,9 +58,6 @@ struct FinishParams {
   int n;
 };
 
-// 24-bit uniform in (0, 1]: ln u is finite.
-__device__ __forceinline__ float u01_open0(uint32_t x) { return (float)((x >> 8) + 1u) * (1.0f / 16777216.0f); }
-
 // ---- begin: the spread restarts at sigma ---------------------------------------
 __global__ __launch_bounds__(qs::kCemThreads) void cem_fill_kernel(FillParams P) {
   const uint64_t t = (uint64_t)blockIdx.x * qs::kCemThreads + threadIdx.x;
@@ -86,50 +65,8 @@ __global__ __launch_bounds__(qs::kCemThreads) void cem_fill_kernel(FillParams P)
   P.std[t] = P.sigma[(int)(t % (uint64_t)P.A)];
 }
 
-// ---- sample: one thread per (candidate, env, drone) of step j = blockIdx.y ------
-// C · E · D is below 2^31 (cem_sizes.h), so the index arithmetic is 32-bit.  Only
-// the normals the action components use are formed.
-__global__ __launch_bounds__(qs::kCemThreads) void cem_sample_kernel(SampleParams P) {
-  const uint32_t v = blockIdx.x * (uint32_t)qs::kCemThreads + threadIdx.x;
-  const uint32_t ED = (uint32_t)P.E * (uint32_t)P.D, per_step = (uint32_t)P.C * ED;
-  if (v >= per_step) return;
-  const int j = blockIdx.y;
-  const uint32_t c = v / ED, ed = v - c * ED, e = ed / (uint32_t)P.D, d = ed - e * (uint32_t)P.D;
-  const size_t at = ((size_t)j * ED + ed) * P.A;
-  const float* mu = P.mean + at;
-  float* out = P.cand + ((size_t)j * per_step + v) * P.A;
-  if (c == 0) {
-    for (int a = 0; a < P.A; ++a) out[a] = mu[a];
-    return;
-  }
-  const float* sd = P.std + at;
-  const uint32_t tick = (uint32_t)*P.tick;
-  const qs::U4 x = qs::philox(qs::U4{tick, P.genv0 + e, c * 32u + (uint32_t)j,
-                                     ((uint32_t)qs::kCemTag << 24) | (P.iter << 8) | d},
-                              P.k0, P.k1);
-  const float two_pi = 6.283185307179586f;
-  float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  const float r0 = sqrtf(-2.0f * logf(u01_open0(x.x))), a0 = two_pi * u01_open0(x.y);
-  z[0] = r0 * cosf(a0);
-  if (P.A > 1) z[1] = r0 * sinf(a0);
-  if (P.A > 2) {   // (kernel-uniform)
-    const float r1 = sqrtf(-2.0f * logf(u01_open0(x.z))), a1 = two_pi * u01_open0(x.w);
-    z[2] = r1 * cosf(a1);
-    z[3] = r1 * sinf(a1);
-  }
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    if (a >= P.A) break;
-    const float sg = sd[a];
-    const float val = sg == 0.0f ? mu[a] : mu[a] + sg * z[a];
-    out[a] = fminf(fmaxf(val, P.lo), P.hi);
-  }
-}
-
 // ---- the order --------------------------------------------------------------------
-__device__ __forceinline__ double score_of(const SelectParams& P, size_t ce) {
-  return P.ret[ce] - (P.first_done[ce] < P.n ? P.penalty : 0.0);
-}
+using qs::score_of;
 // A score as an unsigned key that sorts as the total order wants: larger score,
 // larger key; -0.0 and 0.0 share one key; every NaN gets 0, below -inf's key.
 __device__ __forceinline__ uint64_t key_of(double s) {
@@ -308,27 +245,10 @@ __global__ __launch_bounds__(qs::kCemThreads) void cem_refit_thread_kernel(Refit
   store_fit(P, j, e, k, m, sq / (double)P.K);
 }
 
-// The sum over the whole workgroup of `acc` per component k = tid mod rowp, handed
-// to every thread.  rowp is a power of two, so the lanes of one component sit
-// rowp apart in a wave: an xor tree over the offsets 32 .. rowp sums them, then
-// the partials (one per wave, or one per group where a row spans whole waves)
-// meet in an LDS tree, as in mppi_sum_block_kernel.
+// The sum over the whole workgroup of `acc` per component k = tid mod rowp
+// (block_row_reduce), handed to every thread.
 __device__ __forceinline__ double block_row_sum(double acc, double* part, int tid, int rowp) {
-  const int lane = tid & 63, wave = tid >> 6;
-  int parts;
-  if (rowp <= 64) {
-    for (int off = 32; off >= rowp; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    parts = qs::kCemBlockThreads / 64;
-    if (lane < rowp) part[wave * rowp + lane] = acc;
-  } else {
-    parts = qs::kCemBlockThreads / rowp;
-    part[tid] = acc;   // = part[g * rowp + k]
-  }
-  __syncthreads();
-  for (int s = parts >> 1; s >= 1; s >>= 1) {
-    if (tid < s * rowp) part[tid] += part[tid + s * rowp];
-    __syncthreads();
-  }
+  qs::block_row_reduce(acc, part, tid, rowp);
   const double total = part[tid & (rowp - 1)];
   __syncthreads();   // part is used again
   return total;
@@ -379,16 +299,12 @@ __global__ __launch_bounds__(qs::kCemThreads) void cem_finish_kernel(FinishParam
 
 }  // namespace
 
-struct qs_cem {
-  qs_handle* h = nullptr;
+struct qs_cem : qs::PlannerBase {
   qs_cem_spec spec;
-  qs::HandleInfo info;
-  qs::CemShape shape;
   qs::CemVariant variant;
   qs::CemGrids grids;
   uint64_t bytes[qs::kCemBufs];
   void* buf[qs::kCemBufs];
-  std::vector<const float*> steps;   // candidates' n step pointers, the host array qs_score reads
 };
 
 namespace {
@@ -397,26 +313,28 @@ int begin_impl(qs_cem* p, hipStream_t st) {
   FillParams P;
   P.std = (float*)p->buf[qs::kCemStd];
   P.total = p->bytes[qs::kCemStd] / 4u;
-  P.A = (int)p->shape.A;
+  P.A = p->A;
   for (int a = 0; a < 4; ++a) P.sigma[a] = p->spec.sigma[a];
   hipLaunchKernelGGL(cem_fill_kernel, dim3(p->grids.fill), dim3(qs::kCemThreads), 0, st, P);
-  CEM_HIP_TRY(hipGetLastError());
+  PLANNER_HIP_TRY(hipGetLastError());
   return QS_OK;
 }
 
+// The shared sample kernel round the mean, its spread from `std`: tag 4 and the iteration.
 int sample_impl(qs_cem* p, int iteration, hipStream_t st) {
-  SampleParams P;
+  qs::SampleParams<StdMem> P;
   P.mean = (const float*)p->buf[qs::kCemMean];
-  P.std = (const float*)p->buf[qs::kCemStd];
+  P.spread.std = (const float*)p->buf[qs::kCemStd];
   P.cand = (float*)p->buf[qs::kCemCandidates];
   P.tick = (const uint64_t*)p->buf[qs::kCemTick];
   P.k0 = (uint32_t)p->spec.seed; P.k1 = (uint32_t)(p->spec.seed >> 32);
   P.genv0 = (uint32_t)p->info.env_offset;
-  P.iter = (uint32_t)iteration;
-  P.n = (int)p->shape.n; P.C = (int)p->shape.C; P.E = (int)p->shape.E; P.D = (int)p->shape.D; P.A = (int)p->shape.A;
+  P.tag = (uint32_t)qs::kCemTag; P.iter = (uint32_t)iteration;
+  P.n = p->n; P.C = p->C; P.E = p->E; P.D = p->D; P.A = p->A;
   P.lo = p->spec.lo; P.hi = p->spec.hi;
-  hipLaunchKernelGGL(cem_sample_kernel, dim3(p->grids.sample, (uint32_t)p->shape.n), dim3(qs::kCemThreads), 0, st, P);
-  CEM_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(qs::planner_sample_kernel<StdMem>, dim3(p->grids.sample, (uint32_t)p->n), dim3(qs::kCemThreads), 0, st,
+                     P);
+  PLANNER_HIP_TRY(hipGetLastError());
   return QS_OK;
 }
 
@@ -425,30 +343,30 @@ int refit_impl(qs_cem* p, int iteration, hipStream_t st) {
   S.ret = (const double*)p->buf[qs::kCemRet];
   S.first_done = (const int32_t*)p->buf[qs::kCemFirstDone];
   S.elites = (int32_t*)p->buf[qs::kCemElites];
-  S.iter_best = (double*)p->buf[qs::kCemIterBest] + (size_t)iteration * (size_t)p->shape.E;
+  S.iter_best = (double*)p->buf[qs::kCemIterBest] + (size_t)iteration * (size_t)p->E;
   S.penalty = p->spec.done_penalty;
-  S.n = (int)p->shape.n; S.C = (int)p->shape.C; S.K = (int)p->shape.K; S.E = (int)p->shape.E;
-  S.index_bytes = qs::cem_index_bytes(p->shape.C);
+  S.n = p->n; S.C = p->C; S.K = p->spec.elites; S.E = p->E;
+  S.index_bytes = qs::cem_index_bytes(p->C);
   RefitParams R;
   R.cand = (const float*)p->buf[qs::kCemCandidates];
   R.elites = (const int32_t*)p->buf[qs::kCemElites];
   R.mean = (float*)p->buf[qs::kCemMean];
   R.std = (float*)p->buf[qs::kCemStd];
   R.alpha = p->spec.alpha;
-  R.n = S.n; R.C = S.C; R.K = S.K; R.E = S.E; R.A = (int)p->shape.A;
-  R.row = (int)(p->shape.D * p->shape.A);
+  R.n = S.n; R.C = S.C; R.K = S.K; R.E = S.E; R.A = p->A;
+  R.row = p->D * p->A;
   R.rowp = qs::mppi_row_pow2(R.row);
   for (int a = 0; a < 4; ++a) { R.sigma[a] = p->spec.sigma[a]; R.sigma_min[a] = p->spec.sigma_min[a]; }
   if (p->variant == qs::kCemPerBlock) {
     hipLaunchKernelGGL(cem_select_block_kernel, dim3(p->grids.select), dim3(qs::kCemBlockThreads), 0, st, S);
-    CEM_HIP_TRY(hipGetLastError());
+    PLANNER_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(cem_refit_block_kernel, dim3(p->grids.refit), dim3(qs::kCemBlockThreads), 0, st, R);
   } else {
     hipLaunchKernelGGL(cem_select_thread_kernel, dim3(p->grids.select), dim3(qs::kCemThreads), 0, st, S);
-    CEM_HIP_TRY(hipGetLastError());
+    PLANNER_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(cem_refit_thread_kernel, dim3(p->grids.refit), dim3(qs::kCemThreads), 0, st, R);
   }
-  CEM_HIP_TRY(hipGetLastError());
+  PLANNER_HIP_TRY(hipGetLastError());
   return QS_OK;
 }
 
@@ -458,9 +376,9 @@ int finish_impl(qs_cem* p, hipStream_t st) {
   P.action = (float*)p->buf[qs::kCemAction];
   P.tick = (uint64_t*)p->buf[qs::kCemTick];
   P.col = p->bytes[qs::kCemAction] / 4u;
-  P.n = (int)p->shape.n;
+  P.n = p->n;
   hipLaunchKernelGGL(cem_finish_kernel, dim3(p->grids.finish), dim3(qs::kCemThreads), 0, st, P);
-  CEM_HIP_TRY(hipGetLastError());
+  PLANNER_HIP_TRY(hipGetLastError());
   return QS_OK;
 }
 
@@ -469,40 +387,22 @@ int bad_iteration(const qs_cem* p, int iteration, const char* who) {
                                               " is outside 0 .. iterations - 1 = " + std::to_string(p->spec.iterations - 1));
 }
 
-void free_bufs(qs_cem* p) {
-  for (void* b : p->buf)
-    if (b) (void)hipFree(b);
-}
-
 }  // namespace
 
 extern "C" {
 
 int qs_cem_create(qs_handle* h, const qs_cem_spec* spec, qs_cem** out) {
   using qs::set_last_error;
-  if (!h || !spec || !out) return set_last_error(QS_E_INVALID, "qs_cem_create: null argument");
-  const int depth = qs_score_depth(h);
-  if (depth < 1)
-    return set_last_error(QS_E_INVALID, "qs_cem_create: this handle cannot score (qs_score_depth = 0): a layout whose "
-                                        "reset draws can be rejected, or a Flock / Meetup / LeaderFollower task");
-  if (spec->horizon < 1 || spec->horizon > depth)
-    return set_last_error(QS_E_INVALID, "qs_cem_create: horizon = " + std::to_string(spec->horizon) +
-                                            " is outside 1 .. qs_score_depth = " + std::to_string(depth));
-  if (spec->candidates < 2)
-    return set_last_error(QS_E_INVALID, "qs_cem_create: candidates must be >= 2 (candidate 0 is the mean itself)");
+  const char* who = "qs_cem_create";
+  qs_dims d;
+  if (int rc = qs::planner_check_spec(who, "mean", h, spec, out, &d)) return rc;
   if (spec->elites < 1 || spec->elites > spec->candidates || spec->elites > qs::kCemMaxElites)
     return set_last_error(QS_E_INVALID, "qs_cem_create: elites = " + std::to_string(spec->elites) +
                                             " is outside 1 .. min(candidates, " + std::to_string(qs::kCemMaxElites) + ")");
   if (spec->iterations < 1 || spec->iterations > qs::kCemMaxIterations)
     return set_last_error(QS_E_INVALID, "qs_cem_create: iterations = " + std::to_string(spec->iterations) +
                                             " is outside 1 .. " + std::to_string(qs::kCemMaxIterations));
-  if (!(spec->lo < spec->hi) || !std::isfinite(spec->lo) || !std::isfinite(spec->hi))
-    return set_last_error(QS_E_INVALID, "qs_cem_create: lo must be below hi, both finite");
-  qs_dims d;
-  if (int rc = qs_get_dims(h, &d)) return rc;
   for (int a = 0; a < d.act_dim && a < 4; ++a) {
-    if (!(spec->sigma[a] >= 0.0f) || !std::isfinite(spec->sigma[a]))
-      return set_last_error(QS_E_INVALID, "qs_cem_create: sigma[" + std::to_string(a) + "] must be finite and >= 0");
     if (!(spec->sigma_min[a] >= 0.0f) || !std::isfinite(spec->sigma_min[a]))
       return set_last_error(QS_E_INVALID, "qs_cem_create: sigma_min[" + std::to_string(a) + "] must be finite and >= 0");
     if (spec->sigma_min[a] > spec->sigma[a])
@@ -511,46 +411,18 @@ int qs_cem_create(qs_handle* h, const qs_cem_spec* spec, qs_cem** out) {
   }
   if (!(spec->alpha >= 0.0) || !(spec->alpha < 1.0))
     return set_last_error(QS_E_INVALID, "qs_cem_create: alpha must be in [0, 1)");
-  if (!(spec->done_penalty >= 0.0) || !std::isfinite(spec->done_penalty))
-    return set_last_error(QS_E_INVALID, "qs_cem_create: done_penalty must be finite and >= 0");
-  qs_cem* p = new (std::nothrow) qs_cem;
-  if (!p) return set_last_error(QS_E_NOMEM, "qs_cem_create: out of host memory");
-  p->h = h;
-  p->spec = *spec;
-  qs::handle_info(h, &p->info);
-  p->shape = qs::CemShape{spec->horizon, spec->candidates, spec->elites, spec->iterations, d.num_envs, d.num_drones, d.act_dim};
-  for (void*& b : p->buf) b = nullptr;
-  if (!qs::cem_sizes(p->shape, p->bytes)) {
-    delete p;
-    return set_last_error(QS_E_INVALID, "qs_cem_create: candidates * num_envs * num_drones is too large (the 32-bit "
-                                        "offsets of qs_score, at most 2^27 candidates)");
-  }
-  p->variant = qs::cem_variant(p->shape.E, p->shape.C, p->shape.D * p->shape.A);
-  p->grids = qs::cem_grids(p->shape, p->variant);
-  hipError_t e = hipSetDevice(p->info.device);
-  for (int i = 0; i < qs::kCemBufs && e == hipSuccess; ++i) {
-    e = hipMalloc(&p->buf[i], p->bytes[i]);
-    if (e == hipSuccess) e = hipMemset(p->buf[i], 0, p->bytes[i]);
-  }
-  if (e != hipSuccess) {
-    free_bufs(p);
-    delete p;
-    return set_last_error(e == hipErrorOutOfMemory ? QS_E_NOMEM : QS_E_HIP,
-                          std::string("qs_cem_create: ") + hipGetErrorString(e));
-  }
-  const size_t step = (size_t)(p->bytes[qs::kCemCandidates] / 4u / (uint64_t)p->shape.n);
-  for (int j = 0; j < p->shape.n; ++j) p->steps.push_back((const float*)p->buf[qs::kCemCandidates] + (size_t)j * step);
+  qs_cem* p = qs::planner_new<qs_cem>(who, h, *spec, d);
+  if (!p) return QS_E_NOMEM;
+  const qs::CemShape shape{p->n, p->C, spec->elites, spec->iterations, p->E, p->D, p->A};
+  if (!qs::cem_sizes(shape, p->bytes)) return qs::planner_too_large(who, p);
+  p->variant = qs::cem_variant(shape.E, shape.C, shape.D * shape.A);
+  p->grids = qs::cem_grids(shape, p->variant);
+  if (int rc = qs::planner_alloc(who, p, qs::kCemCandidates)) return rc;
   *out = p;
   return QS_OK;
 }
 
-int qs_cem_destroy(qs_cem* p) {
-  if (!p) return QS_OK;
-  (void)hipSetDevice(p->info.device);   // teardown: best effort
-  free_bufs(p);
-  delete p;
-  return QS_OK;
-}
+int qs_cem_destroy(qs_cem* p) { return qs::planner_destroy(p); }
 
 int qs_cem_buffers(const qs_cem* p, qs_cem_bufs* out) {
   if (!p || !out) return qs::set_last_error(QS_E_INVALID, "qs_cem_buffers: null argument");
@@ -568,14 +440,7 @@ int qs_cem_buffers(const qs_cem* p, qs_cem_bufs* out) {
 
 int qs_cem_reset(qs_cem* p, const float* mean, void* stream) {
   if (!p) return qs::set_last_error(QS_E_INVALID, "qs_cem_reset: null planner");
-  hipStream_t st = (hipStream_t)stream;
-  CEM_HIP_TRY(hipSetDevice(p->info.device));
-  if (mean)
-    CEM_HIP_TRY(hipMemcpyAsync(p->buf[qs::kCemMean], mean, p->bytes[qs::kCemMean], hipMemcpyDeviceToDevice, st));
-  else
-    CEM_HIP_TRY(hipMemsetAsync(p->buf[qs::kCemMean], 0, p->bytes[qs::kCemMean], st));
-  CEM_HIP_TRY(hipMemsetAsync(p->buf[qs::kCemTick], 0, p->bytes[qs::kCemTick], st));
-  return QS_OK;
+  return qs::planner_reset(p, qs::kCemMean, qs::kCemTick, mean, (hipStream_t)stream);
 }
 
 int qs_cem_begin(qs_cem* p, void* stream) {
@@ -602,14 +467,12 @@ int qs_cem_finish(qs_cem* p, void* stream) {
 
 int qs_cem_plan(qs_cem* p, void* stream) {
   if (!p) return qs::set_last_error(QS_E_INVALID, "qs_cem_plan: null planner");
-  qs::handle_info(p->h, &p->info);
-  if (!p->info.reset_done) return qs::set_last_error(QS_E_STATE, "qs_cem_plan: call qs_reset first");
+  if (int rc = qs::planner_ready("qs_cem_plan", p)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (int rc = begin_impl(p, st)) return rc;
-  const qs_score_out so{p->buf[qs::kCemRet], (int32_t*)p->buf[qs::kCemFirstDone]};
   for (int i = 0; i < p->spec.iterations; ++i) {
     if (int rc = sample_impl(p, i, st)) return rc;
-    if (int rc = qs_score(p->h, (int)p->shape.n, (int)p->shape.C, p->steps.data(), nullptr, &so, stream)) return rc;
+    if (int rc = qs::planner_score(p, p->buf[qs::kCemRet], p->buf[qs::kCemFirstDone], stream)) return rc;
     if (int rc = refit_impl(p, i, st)) return rc;
   }
   return finish_impl(p, st);

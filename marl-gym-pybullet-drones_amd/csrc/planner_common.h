@@ -1,0 +1,238 @@
+// planner_common.h — what the MPPI tick (planner.hip) and the CEM tick
+// (planner_cem.hip) share: the sample kernel, the penalised score, the row
+// reduction of the per-workgroup variants, and the host record with its create /
+// destroy / reset / score plumbing.  HIP; included by those two files only.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+#include <new>
+
+#include "quadswarm.h"
+#include "planner_link.h"
+#include "planner_sizes.h"
+#include "step_kernel.h"   // qs::philox
+
+#define PLANNER_HIP_TRY(expr)                                                                     \
+  do {                                                                                            \
+    hipError_t _e = (expr);                                                                       \
+    if (_e != hipSuccess) return qs::set_last_error(QS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+  } while (0)
+
+namespace qs {
+
+// ---- device ------------------------------------------------------------------------
+// Spread is where the sample kernel reads a component's standard deviation from:
+// `float at(size_t i, int a) const`, i the element's offset in [n][E][D][A].
+template <class Spread>
+struct SampleParams {
+  const float* mean;         // [n][E][D][A]: the sequence the candidates are drawn round
+  float* cand;               // [n][C][E][D][A]
+  const uint64_t* tick;
+  uint32_t k0, k1, genv0, tag, iter;   // Philox key, global id of env 0, domain tag, iteration
+  int n, C, E, D, A;
+  float lo, hi;
+  Spread spread;
+};
+
+// 24-bit uniform in (0, 1]: ln u is finite.
+__device__ __forceinline__ float u01_open0(uint32_t x) { return (float)((x >> 8) + 1u) * (1.0f / 16777216.0f); }
+
+// One thread per (candidate, env, drone) of step j = blockIdx.y: C · E · D is below
+// 2^31 (planner_sizes.h), so the index arithmetic is 32-bit.  Candidate 0 is the
+// mean itself.  Only the normals the action components use are formed (the second
+// Box–Muller pair from A = 3 on).
+template <class Spread>
+__global__ __launch_bounds__(kPlannerThreads) void planner_sample_kernel(SampleParams<Spread> P) {
+  const uint32_t v = blockIdx.x * (uint32_t)kPlannerThreads + threadIdx.x;
+  const uint32_t ED = (uint32_t)P.E * (uint32_t)P.D, per_step = (uint32_t)P.C * ED;
+  if (v >= per_step) return;
+  const int j = blockIdx.y;
+  const uint32_t c = v / ED, ed = v - c * ED, e = ed / (uint32_t)P.D, d = ed - e * (uint32_t)P.D;
+  const size_t at = ((size_t)j * ED + ed) * P.A;
+  const float* mu = P.mean + at;
+  float* out = P.cand + ((size_t)j * per_step + v) * P.A;
+  if (c == 0) {
+    for (int a = 0; a < P.A; ++a) out[a] = mu[a];
+    return;
+  }
+  const uint32_t tick = (uint32_t)*P.tick;
+  const U4 x = philox(U4{tick, P.genv0 + e, c * 32u + (uint32_t)j, (P.tag << 24) | (P.iter << 8) | d}, P.k0, P.k1);
+  const float two_pi = 6.283185307179586f;
+  float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  const float r0 = sqrtf(-2.0f * logf(u01_open0(x.x))), a0 = two_pi * u01_open0(x.y);
+  z[0] = r0 * cosf(a0);
+  if (P.A > 1) z[1] = r0 * sinf(a0);
+  if (P.A > 2) {   // (kernel-uniform)
+    const float r1 = sqrtf(-2.0f * logf(u01_open0(x.z))), a1 = two_pi * u01_open0(x.w);
+    z[2] = r1 * cosf(a1);
+    z[3] = r1 * sinf(a1);
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    if (a >= P.A) break;
+    const float sg = P.spread.at(at, a);
+    const float val = sg == 0.0f ? mu[a] : mu[a] + sg * z[a];
+    out[a] = fminf(fmaxf(val, P.lo), P.hi);
+  }
+}
+
+// A candidate's return, less the penalty where it ends an episode inside the n steps.
+__device__ __forceinline__ double penalised_score(const double* ret, const int32_t* first_done, int n, double penalty,
+                                                  size_t ce) {
+  return ret[ce] - (first_done[ce] < n ? penalty : 0.0);
+}
+// ... from a kernel's parameter record that holds ret, first_done, n and penalty.
+template <class Params>
+__device__ __forceinline__ double score_of(const Params& P, size_t ce) {
+  return penalised_score(P.ret, P.first_done, P.n, P.penalty, ce);
+}
+
+// The sums over a kPlannerBlockThreads workgroup of `acc` per component
+// k = tid mod rowp, left in part[0 .. rowp) (part holds kPlannerBlockThreads
+// doubles).  rowp is a power of two, so the lanes of one component sit rowp apart
+// in a wave: an xor tree over the offsets 32 .. rowp sums them, then the partials
+// (one per wave, or one per group where a row spans whole waves) meet in an LDS
+// tree, whose last step ends in a barrier.
+__device__ __forceinline__ void block_row_reduce(double acc, double* part, int tid, int rowp) {
+  const int lane = tid & 63, wave = tid >> 6;
+  int parts;
+  if (rowp <= 64) {
+    for (int off = 32; off >= rowp; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    parts = kPlannerBlockThreads / 64;
+    if (lane < rowp) part[wave * rowp + lane] = acc;
+  } else {
+    parts = kPlannerBlockThreads / rowp;
+    part[tid] = acc;   // = part[g * rowp + k]
+  }
+  __syncthreads();
+  for (int s = parts >> 1; s >= 1; s >>= 1) {
+    if (tid < s * rowp) part[tid] += part[tid + s * rowp];
+    __syncthreads();
+  }
+}
+
+// ---- host --------------------------------------------------------------------------
+// What qs_mppi and qs_cem both are.  The derived records add `spec`, `variant`,
+// `grids`, `bytes[]` and `buf[]`.
+struct PlannerBase {
+  qs_handle* h = nullptr;
+  HandleInfo info;
+  int n, C, E, D, A;
+  std::vector<const float*> steps;   // candidates' n step pointers, the host array qs_score reads
+};
+
+// The checks every planner spec goes through (`who`: the entry point, `centre`:
+// what candidate 0 is); fills `d`.
+template <class Spec>
+int planner_check_spec(const char* who, const char* centre, qs_handle* h, const Spec* spec, const void* out, qs_dims* d) {
+  const std::string w = std::string(who) + ": ";
+  if (!h || !spec || !out) return set_last_error(QS_E_INVALID, w + "null argument");
+  const int depth = qs_score_depth(h);
+  if (depth < 1)
+    return set_last_error(QS_E_INVALID, w + "this handle cannot score (qs_score_depth = 0): a layout whose "
+                                            "reset draws can be rejected, or a Flock / Meetup / LeaderFollower task");
+  if (spec->horizon < 1 || spec->horizon > depth)
+    return set_last_error(QS_E_INVALID, w + "horizon = " + std::to_string(spec->horizon) +
+                                            " is outside 1 .. qs_score_depth = " + std::to_string(depth));
+  if (spec->candidates < 2)
+    return set_last_error(QS_E_INVALID, w + "candidates must be >= 2 (candidate 0 is the " + centre + " itself)");
+  if (!(spec->lo < spec->hi) || !std::isfinite(spec->lo) || !std::isfinite(spec->hi))
+    return set_last_error(QS_E_INVALID, w + "lo must be below hi, both finite");
+  if (int rc = qs_get_dims(h, d)) return rc;
+  for (int a = 0; a < d->act_dim && a < 4; ++a)
+    if (!(spec->sigma[a] >= 0.0f) || !std::isfinite(spec->sigma[a]))
+      return set_last_error(QS_E_INVALID, w + "sigma[" + std::to_string(a) + "] must be finite and >= 0");
+  if (!(spec->done_penalty >= 0.0) || !std::isfinite(spec->done_penalty))
+    return set_last_error(QS_E_INVALID, w + "done_penalty must be finite and >= 0");
+  return QS_OK;
+}
+
+// A fresh record with its shape and its buffer pointers cleared; null (and the error set) without memory.
+template <class T, class Spec>
+T* planner_new(const char* who, qs_handle* h, const Spec& spec, const qs_dims& d) {
+  T* p = new (std::nothrow) T;
+  if (!p) {
+    set_last_error(QS_E_NOMEM, std::string(who) + ": out of host memory");
+    return nullptr;
+  }
+  p->h = h;
+  p->spec = spec;
+  handle_info(h, &p->info);
+  p->n = spec.horizon; p->C = spec.candidates; p->E = d.num_envs; p->D = d.num_drones; p->A = d.act_dim;
+  for (void*& b : p->buf) b = nullptr;
+  return p;
+}
+
+// The refusal of a shape *_sizes turns down; deletes the record.
+template <class T>
+int planner_too_large(const char* who, T* p) {
+  delete p;
+  return set_last_error(QS_E_INVALID, std::string(who) + ": candidates * num_envs * num_drones is too large (the 32-bit "
+                                                         "offsets of qs_score, at most 2^27 candidates)");
+}
+
+template <class T>
+void planner_free(T* p) {
+  for (void* b : p->buf)
+    if (b) (void)hipFree(b);
+}
+
+// Allocates and zeroes every buffer of p->bytes and points `steps` into buffer
+// `candidates`; on failure frees what it made and deletes the record.
+template <class T>
+int planner_alloc(const char* who, T* p, int candidates) {
+  constexpr int kBufs = sizeof(p->buf) / sizeof(p->buf[0]);
+  hipError_t e = hipSetDevice(p->info.device);
+  for (int i = 0; i < kBufs && e == hipSuccess; ++i) {
+    e = hipMalloc(&p->buf[i], p->bytes[i]);
+    if (e == hipSuccess) e = hipMemset(p->buf[i], 0, p->bytes[i]);
+  }
+  if (e != hipSuccess) {
+    planner_free(p);
+    delete p;
+    return set_last_error(e == hipErrorOutOfMemory ? QS_E_NOMEM : QS_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  }
+  const size_t step = (size_t)(p->bytes[candidates] / 4u / (uint64_t)p->n);
+  for (int j = 0; j < p->n; ++j) p->steps.push_back((const float*)p->buf[candidates] + (size_t)j * step);
+  return QS_OK;
+}
+
+template <class T>
+int planner_destroy(T* p) {
+  if (!p) return QS_OK;
+  (void)hipSetDevice(p->info.device);   // teardown: best effort
+  planner_free(p);
+  delete p;
+  return QS_OK;
+}
+
+// Buffer `seq` becomes a copy of `src` (device memory; null: zeros) and the tick 0.
+template <class T>
+int planner_reset(T* p, int seq, int tick, const float* src, hipStream_t st) {
+  PLANNER_HIP_TRY(hipSetDevice(p->info.device));
+  if (src)
+    PLANNER_HIP_TRY(hipMemcpyAsync(p->buf[seq], src, p->bytes[seq], hipMemcpyDeviceToDevice, st));
+  else
+    PLANNER_HIP_TRY(hipMemsetAsync(p->buf[seq], 0, p->bytes[seq], st));
+  PLANNER_HIP_TRY(hipMemsetAsync(p->buf[tick], 0, p->bytes[tick], st));
+  return QS_OK;
+}
+
+// plan()'s gate: the handle's state as it is now, refused before qs_reset.
+inline int planner_ready(const char* who, PlannerBase* p) {
+  handle_info(p->h, &p->info);
+  if (!p->info.reset_done) return set_last_error(QS_E_STATE, std::string(who) + ": call qs_reset first");
+  return QS_OK;
+}
+
+// Scores the candidates from the handle's current state into ret / first_done.
+inline int planner_score(PlannerBase* p, void* ret, void* first_done, void* stream) {
+  const qs_score_out so{ret, (int32_t*)first_done};
+  return qs_score(p->h, p->n, p->C, p->steps.data(), nullptr, &so, stream);
+}
+
+}  // namespace qs

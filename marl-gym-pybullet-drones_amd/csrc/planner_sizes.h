@@ -15,8 +15,10 @@ namespace qs {
 
 constexpr int kMppiMaxSteps = 32;          // = kScoreMaxSteps (step_score.h): the counter word holds c · 32 + j
 constexpr int kMppiTag = 3;                // Philox domain tag of the planner's noise (1: actions, 2: reset tries)
-constexpr int kMppiThreads = 256;          // workgroup of the sample kernel and of the per-thread variants
-constexpr int kMppiSumThreads = 1024;      // workgroup of the per-workgroup weights and weighted sum (16 waves)
+constexpr int kPlannerThreads = 256;       // workgroup of the sample kernel and of both planners' per-thread variants
+constexpr int kPlannerBlockThreads = 1024; // workgroup of both planners' per-workgroup variants (16 waves)
+constexpr int kMppiThreads = kPlannerThreads;
+constexpr int kMppiSumThreads = kPlannerBlockThreads;   // the per-workgroup weights and weighted sum
 constexpr int kMppiMaxRow = 256;           // D · A at most (D <= 64, A <= 4)
 constexpr int64_t kMppiMaxCandidates = int64_t(1) << 27;   // c · 32 + j stays inside one 32-bit counter word
 

@@ -429,7 +429,79 @@ class _DeviceSpan:
                                          "version": 2, "strides": None}
 
 
-class MPPIPlanner:
+class _Planner:
+    """What `MPPIPlanner` and `CEMPlanner` share: creation through the entry
+    points `<_PREFIX>_*`, the device views, `plan`, `step_t` and `close`."""
+
+    _PREFIX = None   # "qs_mppi" / "qs_cem"
+
+    def _bind(self, swarm):
+        self.swarm, self.lib = swarm, swarm.lib
+        if not hasattr(self.lib, f"{self._PREFIX}_create"):
+            raise L.QuadSwarmError(f"{L.LIB_PATH} has no {self._PREFIX}_create: rebuild the HIP extension")
+
+    def _per_component(self, v, what):
+        A = self.swarm.act_dim
+        out = [float(v)] * A if np.isscalar(v) else [float(s) for s in v]
+        if len(out) != A:
+            raise ValueError(f"{what} must be a number or one per action component ({A})")
+        return out
+
+    def _call(self, name, *args):
+        fn = f"{self._PREFIX}_{name}"
+        L.check(getattr(self.lib, fn)(self._p, *args, self._stream()), fn)
+
+    def _create(self, spec, bufs, views):
+        """`<_PREFIX>_create(spec)`, then one attribute per (name, shape, typestr)
+        of `views`: a tensor over that member of `bufs`."""
+        swarm = self.swarm
+        self.spec = spec
+        self._p = ctypes.c_void_p()
+        self._stepper = swarm.step   # what step_t runs the action with (SwarmVecEnv.mppi / .cem: its step_t)
+        with torch.cuda.device(swarm.device):
+            L.check(getattr(self.lib, f"{self._PREFIX}_create")(swarm._h, ctypes.byref(spec), ctypes.byref(self._p)),
+                    f"{self._PREFIX}_create")
+        L.check(getattr(self.lib, f"{self._PREFIX}_buffers")(self._p, ctypes.byref(bufs)), f"{self._PREFIX}_buffers")
+        for name, shape, typestr in views:
+            setattr(self, name, torch.as_tensor(_DeviceSpan(getattr(bufs, name), shape, typestr), device=swarm.device))
+
+    def _stream(self):
+        return self.swarm._stream()
+
+    def _reset(self, seq, name):
+        """`<_PREFIX>_reset` with `seq` (None: zeros) for the buffer `name`."""
+        if seq is not None:
+            shape = tuple(getattr(self, name).shape)
+            if (not isinstance(seq, torch.Tensor) or seq.dtype != torch.float32 or not seq.is_contiguous()
+                    or seq.device != self.swarm.device or tuple(seq.shape) != shape):
+                raise ValueError(f"{name} must be a contiguous float32 {shape} tensor on {self.swarm.device}")
+        self._call("reset", L.ptr(seq))
+
+    def plan(self):
+        """One planner tick from the swarm's current state; returns `action`."""
+        self._call("plan")
+        return self.action
+
+    def step_t(self, **bufs):
+        """One receding-horizon tick: `plan()`, then the control step that runs
+        `action` (the swarm's `step`, or `SwarmVecEnv.step_t`), with its return."""
+        self.plan()
+        return self._stepper(self.action, **bufs)
+
+    def close(self):
+        if getattr(self, "_p", None):
+            torch.cuda.synchronize(self.swarm.device)
+            getattr(self.lib, f"{self._PREFIX}_destroy")(self._p)
+            self._p = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MPPIPlanner(_Planner):
     """The native MPPI tick round `QuadSwarm.score` (qs_mppi_*, include/quadswarm.h).
 
     `sample()` draws `candidates` sequences round `nominal` (candidate 0 is the
@@ -446,85 +518,36 @@ class MPPIPlanner:
     float64, best (E,) int32, action (E, D, A), tick (1,) (the uint64 counter,
     viewed as int64).  The swarm must outlive the planner."""
 
+    _PREFIX = "qs_mppi"
+
     def __init__(self, swarm, horizon, candidates, sigma, lo=-1.0, hi=1.0, lam=1.0, done_penalty=0.0, seed=0):
-        self.swarm, self.lib = swarm, swarm.lib
-        if not hasattr(self.lib, "qs_mppi_create"):
-            raise L.QuadSwarmError(f"{L.LIB_PATH} has no qs_mppi_create: rebuild the HIP extension")
-        A = swarm.act_dim
-        sig = [float(sigma)] * A if np.isscalar(sigma) else [float(s) for s in sigma]
-        if len(sig) != A:
-            raise ValueError(f"sigma must be a number or one per action component ({A})")
+        self._bind(swarm)
+        sig = self._per_component(sigma, "sigma")
         spec = L.QsMppiSpec()
         spec.horizon, spec.candidates = int(horizon), int(candidates)
-        for a in range(A):
-            spec.sigma[a] = sig[a]
+        for a, s in enumerate(sig):
+            spec.sigma[a] = s
         spec.lo, spec.hi, spec.lambda_, spec.done_penalty = float(lo), float(hi), float(lam), float(done_penalty)
         spec.seed = int(seed)
-        self.spec = spec
         self.horizon, self.num_candidates = int(horizon), int(candidates)
-        self._p = ctypes.c_void_p()
-        self._stepper = swarm.step   # what step_t runs the action with (SwarmVecEnv.mppi: its step_t)
-        with torch.cuda.device(swarm.device):
-            L.check(self.lib.qs_mppi_create(swarm._h, ctypes.byref(spec), ctypes.byref(self._p)), "qs_mppi_create")
-        bufs = L.QsMppiBufs()
-        L.check(self.lib.qs_mppi_buffers(self._p, ctypes.byref(bufs)), "qs_mppi_buffers")
-        n, C, E, D = self.horizon, self.num_candidates, swarm.num_envs, swarm.num_drones
-
-        def view(ptr, shape, typestr):
-            return torch.as_tensor(_DeviceSpan(ptr, shape, typestr), device=swarm.device)
-
-        self.nominal = view(bufs.nominal, (n, E, D, A), "<f4")
-        self.candidates = view(bufs.candidates, (n, C, E, D, A), "<f4")
-        self.ret = view(bufs.ret, (C, E), "<f8")
-        self.first_done = view(bufs.first_done, (C, E), "<i4")
-        self.weights = view(bufs.weights, (C, E), "<f8")
-        self.best = view(bufs.best, (E,), "<i4")
-        self.action = view(bufs.action, (E, D, A), "<f4")
-        self.tick = view(bufs.tick, (1,), "<i8")
-
-    def _stream(self):
-        return self.swarm._stream()
+        n, C, E, D, A = self.horizon, self.num_candidates, swarm.num_envs, swarm.num_drones, swarm.act_dim
+        self._create(spec, L.QsMppiBufs(), (
+            ("nominal", (n, E, D, A), "<f4"), ("candidates", (n, C, E, D, A), "<f4"), ("ret", (C, E), "<f8"),
+            ("first_done", (C, E), "<i4"), ("weights", (C, E), "<f8"), ("best", (E,), "<i4"),
+            ("action", (E, D, A), "<f4"), ("tick", (1,), "<i8")))
 
     def reset(self, nominal=None):
         """Set the nominal sequence ((n, E, D, A) float32 on the device; None: zeros) and tick = 0."""
-        if nominal is not None:
-            if (not isinstance(nominal, torch.Tensor) or nominal.dtype != torch.float32 or not nominal.is_contiguous()
-                    or nominal.device != self.swarm.device or tuple(nominal.shape) != tuple(self.nominal.shape)):
-                raise ValueError(f"nominal must be a contiguous float32 {tuple(self.nominal.shape)} tensor on "
-                                 f"{self.swarm.device}")
-        L.check(self.lib.qs_mppi_reset(self._p, L.ptr(nominal), self._stream()), "qs_mppi_reset")
+        self._reset(nominal, "nominal")
 
     def sample(self):
-        L.check(self.lib.qs_mppi_sample(self._p, self._stream()), "qs_mppi_sample")
+        self._call("sample")
 
     def update(self):
-        L.check(self.lib.qs_mppi_update(self._p, self._stream()), "qs_mppi_update")
-
-    def plan(self):
-        """One planner tick from the swarm's current state; returns `action`."""
-        L.check(self.lib.qs_mppi_plan(self._p, self._stream()), "qs_mppi_plan")
-        return self.action
-
-    def step_t(self, **bufs):
-        """One receding-horizon tick: `plan()`, then the control step that runs
-        `action` (the swarm's `step`, or `SwarmVecEnv.step_t`), with its return."""
-        self.plan()
-        return self._stepper(self.action, **bufs)
-
-    def close(self):
-        if getattr(self, "_p", None):
-            torch.cuda.synchronize(self.swarm.device)
-            self.lib.qs_mppi_destroy(self._p)
-            self._p = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("update")
 
 
-class CEMPlanner:
+class CEMPlanner(_Planner):
     """The native CEM tick round `QuadSwarm.score` (qs_cem_*, include/quadswarm.h).
 
     `begin()` restarts the spread `std` at sigma; `sample(i)` draws `candidates`
@@ -543,93 +566,39 @@ class CEMPlanner:
     int32, iter_best (I, E) float64, action (E, D, A), tick (1,) (the uint64
     counter, viewed as int64).  The swarm must outlive the planner."""
 
+    _PREFIX = "qs_cem"
+
     def __init__(self, swarm, horizon, candidates, elites, sigma, iterations=3, lo=-1.0, hi=1.0, alpha=0.0,
                  sigma_min=0.0, done_penalty=0.0, seed=0):
-        self.swarm, self.lib = swarm, swarm.lib
-        if not hasattr(self.lib, "qs_cem_create"):
-            raise L.QuadSwarmError(f"{L.LIB_PATH} has no qs_cem_create: rebuild the HIP extension")
-        A = swarm.act_dim
-
-        def per_component(v, what):
-            out = [float(v)] * A if np.isscalar(v) else [float(s) for s in v]
-            if len(out) != A:
-                raise ValueError(f"{what} must be a number or one per action component ({A})")
-            return out
-
-        sig, smin = per_component(sigma, "sigma"), per_component(sigma_min, "sigma_min")
+        self._bind(swarm)
+        sig, smin = self._per_component(sigma, "sigma"), self._per_component(sigma_min, "sigma_min")
         spec = L.QsCemSpec()
         spec.horizon, spec.candidates, spec.elites, spec.iterations = int(horizon), int(candidates), int(elites), int(iterations)
-        for a in range(A):
+        for a in range(len(sig)):
             spec.sigma[a], spec.sigma_min[a] = sig[a], smin[a]
         spec.lo, spec.hi, spec.alpha, spec.done_penalty = float(lo), float(hi), float(alpha), float(done_penalty)
         spec.seed = int(seed)
-        self.spec = spec
         self.horizon, self.num_candidates, self.num_elites, self.iterations = (int(horizon), int(candidates), int(elites),
                                                                                int(iterations))
-        self._p = ctypes.c_void_p()
-        self._stepper = swarm.step   # what step_t runs the action with (SwarmVecEnv.cem: its step_t)
-        with torch.cuda.device(swarm.device):
-            L.check(self.lib.qs_cem_create(swarm._h, ctypes.byref(spec), ctypes.byref(self._p)), "qs_cem_create")
-        bufs = L.QsCemBufs()
-        L.check(self.lib.qs_cem_buffers(self._p, ctypes.byref(bufs)), "qs_cem_buffers")
-        n, C, K, I, E, D = self.horizon, self.num_candidates, self.num_elites, self.iterations, swarm.num_envs, swarm.num_drones
-
-        def view(ptr, shape, typestr):
-            return torch.as_tensor(_DeviceSpan(ptr, shape, typestr), device=swarm.device)
-
-        self.mean = view(bufs.mean, (n, E, D, A), "<f4")
-        self.std = view(bufs.std, (n, E, D, A), "<f4")
-        self.candidates = view(bufs.candidates, (n, C, E, D, A), "<f4")
-        self.ret = view(bufs.ret, (C, E), "<f8")
-        self.first_done = view(bufs.first_done, (C, E), "<i4")
-        self.elites = view(bufs.elites, (K, E), "<i4")
-        self.iter_best = view(bufs.iter_best, (I, E), "<f8")
-        self.action = view(bufs.action, (E, D, A), "<f4")
-        self.tick = view(bufs.tick, (1,), "<i8")
-
-    def _stream(self):
-        return self.swarm._stream()
+        n, C, K, I = self.horizon, self.num_candidates, self.num_elites, self.iterations
+        E, D, A = swarm.num_envs, swarm.num_drones, swarm.act_dim
+        self._create(spec, L.QsCemBufs(), (
+            ("mean", (n, E, D, A), "<f4"), ("std", (n, E, D, A), "<f4"), ("candidates", (n, C, E, D, A), "<f4"),
+            ("ret", (C, E), "<f8"), ("first_done", (C, E), "<i4"), ("elites", (K, E), "<i4"),
+            ("iter_best", (I, E), "<f8"), ("action", (E, D, A), "<f4"), ("tick", (1,), "<i8")))
 
     def reset(self, mean=None):
         """Set the mean sequence ((n, E, D, A) float32 on the device; None: zeros) and tick = 0."""
-        if mean is not None:
-            if (not isinstance(mean, torch.Tensor) or mean.dtype != torch.float32 or not mean.is_contiguous()
-                    or mean.device != self.swarm.device or tuple(mean.shape) != tuple(self.mean.shape)):
-                raise ValueError(f"mean must be a contiguous float32 {tuple(self.mean.shape)} tensor on "
-                                 f"{self.swarm.device}")
-        L.check(self.lib.qs_cem_reset(self._p, L.ptr(mean), self._stream()), "qs_cem_reset")
+        self._reset(mean, "mean")
 
     def begin(self):
-        L.check(self.lib.qs_cem_begin(self._p, self._stream()), "qs_cem_begin")
+        self._call("begin")
 
     def sample(self, iteration=0):
-        L.check(self.lib.qs_cem_sample(self._p, int(iteration), self._stream()), "qs_cem_sample")
+        self._call("sample", int(iteration))
 
     def refit(self, iteration=0):
-        L.check(self.lib.qs_cem_refit(self._p, int(iteration), self._stream()), "qs_cem_refit")
+        self._call("refit", int(iteration))
 
     def finish(self):
-        L.check(self.lib.qs_cem_finish(self._p, self._stream()), "qs_cem_finish")
-
-    def plan(self):
-        """One planner tick from the swarm's current state; returns `action`."""
-        L.check(self.lib.qs_cem_plan(self._p, self._stream()), "qs_cem_plan")
-        return self.action
-
-    def step_t(self, **bufs):
-        """One receding-horizon tick: `plan()`, then the control step that runs
-        `action` (the swarm's `step`, or `SwarmVecEnv.step_t`), with its return."""
-        self.plan()
-        return self._stepper(self.action, **bufs)
-
-    def close(self):
-        if getattr(self, "_p", None):
-            torch.cuda.synchronize(self.swarm.device)
-            self.lib.qs_cem_destroy(self._p)
-            self._p = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("finish")

@@ -24,63 +24,19 @@
 import numpy as np
 import pytest
 import torch
-from scipy import stats
 
 from gym_pybullet_drones_amd import _lib as L
 from gym_pybullet_drones_amd.envs.swarm import CEMPlanner, QuadSwarm, grid_layout
 from gym_pybullet_drones_amd.vec_env.vec_env import SwarmVecEnv
+from planner_case import A4, F64, c3, fingerprint, ks_normal, planner_bytes, prepared, same_bytes
+from planner_case import random_sequence as random_mean
 
 pytestmark = pytest.mark.gpu
 
-BLOCKS = (L.STATE_AGENT, L.STATE_ENV, L.STATE_HISTORY, L.STATE_EP_RETURN)
 BUFS = ("mean", "std", "candidates", "ret", "first_done", "elites", "iter_best", "action", "tick")
 STAGE = 4096   # cem_sizes.h kCemStage: the keys the per-workgroup select keeps in LDS
-
-
-def c3(E, **kw):
-    return dict(task="multihover", num_drones=8, num_envs=E, act="one_d_pid", initial_xyzs=grid_layout(8), **kw)
-
-
-A4 = dict(task="multihover", num_drones=3, num_envs=5, act="vel", physics="pyb", initial_xyzs=grid_layout(3))
-F64 = c3(5, precision=8)
 # (E, C, K) of the two variants (cem_variant: a workgroup per env from C = 64 on while E * D * A < 16 384)
 THREAD, BLOCK = (21, 9, 3), (2, 130, 7)
-
-
-def raw(t):
-    return t.cpu().numpy().tobytes() if isinstance(t, torch.Tensor) else np.ascontiguousarray(t).tobytes()
-
-
-def same_bytes(a, b, what):
-    assert tuple(a.shape) == tuple(b.shape) and raw(a) == raw(b), what
-
-
-def fingerprint(sw):
-    """Everything plan() promises to leave alone, as bytes."""
-    torch.cuda.synchronize()
-    recs, total = sw.episode_log()
-    return ([raw(sw.get_state(blk)) for blk in BLOCKS], raw(recs), total, sw.reset_error(), sw.launch_counts())
-
-
-def planner_bytes(pl):
-    torch.cuda.synchronize()
-    return [raw(getattr(pl, k)) for k in BUFS]
-
-
-def prepared(cfg, seed=3, warm=2, twins=0):
-    """`twins` + 1 swarms in the same mid-episode state."""
-    out = [QuadSwarm(**cfg) for _ in range(twins + 1)]
-    for sw in out:
-        sw.reset(seed)
-        for _ in range(warm):
-            sw.step(None)
-    return out
-
-
-def random_mean(pl, seed=11, scale=1.0):
-    """A mean sequence of distinct values in (-scale, scale): candidate 0 equals no other candidate."""
-    gen = torch.Generator(device="cpu").manual_seed(seed)
-    return ((torch.rand(tuple(pl.mean.shape), generator=gen) * 2 - 1) * scale).to(pl.mean.device)
 
 
 def score(sw, pl):
@@ -197,18 +153,6 @@ def test_a_zero_spread_copies_its_component():
     assert torch.equal(pl.candidates[..., 1], m0[:, None, ..., 1].expand(-1, 40, -1, -1))
     assert not torch.equal(pl.candidates[:, 1, ..., 0], m0[..., 0])
     sw.close()
-
-
-def ks_normal(x):
-    """One-sample KS against N(0, 1) at the 0.001 level, mean and variance within 4 standard errors."""
-    x = np.asarray(x, np.float64).ravel()
-    N = x.size
-    assert N >= 1 << 16
-    d = stats.kstest(x, "norm").statistic
-    print(f"N = {N}: KS {d:.5f} (critical {1.95 / np.sqrt(N):.5f}), mean {x.mean():+.5f}, var {x.var(ddof=1):.5f}")
-    assert d < 1.95 / np.sqrt(N)
-    assert abs(x.mean()) < 4 / np.sqrt(N)
-    assert abs(x.var(ddof=1) - 1) < 4 * np.sqrt(2 / (N - 1))
 
 
 def test_noise_over_a_hand_set_std_is_standard_normal():
@@ -439,7 +383,7 @@ def test_plan_equals_its_phases(E, C, K, I):
             score(b, pb)
             pb.refit(it)
         pb.finish()
-        for k, x, y in zip(BUFS, planner_bytes(pa), planner_bytes(pb)):
+        for k, x, y in zip(BUFS, planner_bytes(pa, BUFS), planner_bytes(pb, BUFS)):
             assert x == y, f"{k}, tick {tick}"
     a.close()
     b.close()
@@ -498,10 +442,10 @@ def test_refusals_leave_swarm_and_planner_alone():
     depth = sw.score_depth()
     pl = sw.cem(depth, 9, 3, 0.3, iterations=2, seed=4)       # creating a planner needs no reset
     pl.reset(random_mean(pl))
-    held = planner_bytes(pl)
+    held = planner_bytes(pl, BUFS)
     with pytest.raises(L.QuadSwarmError, match="rc=-4.*qs_reset"):   # QS_E_STATE: plan before qs_reset
         pl.plan()
-    assert planner_bytes(pl) == held
+    assert planner_bytes(pl, BUFS) == held
     sw.reset(3)
     sw.step(None)
     before = fingerprint(sw)
@@ -528,7 +472,7 @@ def test_refusals_leave_swarm_and_planner_alone():
         sw.cem(4, 9, 3, 0.3, sigma_min=(0.1, 0.2))
     with pytest.raises(ValueError):
         pl.reset(torch.zeros((depth, 21, 8), device=sw.device))
-    assert fingerprint(sw) == before and planner_bytes(pl) == held
+    assert fingerprint(sw) == before and planner_bytes(pl, BUFS) == held
     pl.plan()                                                      # and the planner still works
     torch.cuda.synchronize()
     assert int(pl.tick.item()) == 1

@@ -17,63 +17,16 @@
 import numpy as np
 import pytest
 import torch
-from scipy import stats
 
 from gym_pybullet_drones_amd import _lib as L
-from gym_pybullet_drones_amd.envs.swarm import MPPIPlanner, QuadSwarm, grid_layout
+from gym_pybullet_drones_amd.envs.swarm import MPPIPlanner, QuadSwarm
 from gym_pybullet_drones_amd.vec_env.vec_env import SwarmVecEnv
+from planner_case import A4, F64, c3, fingerprint, ks_normal, planner_bytes, prepared, same_bytes
+from planner_case import random_sequence as random_nominal
 
 pytestmark = pytest.mark.gpu
 
-BLOCKS = (L.STATE_AGENT, L.STATE_ENV, L.STATE_HISTORY, L.STATE_EP_RETURN)
-
-
-def c3(E, **kw):
-    return dict(task="multihover", num_drones=8, num_envs=E, act="one_d_pid", initial_xyzs=grid_layout(8), **kw)
-
-
-A4 = dict(task="multihover", num_drones=3, num_envs=5, act="vel", physics="pyb", initial_xyzs=grid_layout(3))
-F64 = c3(5, precision=8)
-
-
-def raw(t):
-    return t.cpu().numpy().tobytes() if isinstance(t, torch.Tensor) else np.ascontiguousarray(t).tobytes()
-
-
-def same_bytes(a, b, what):
-    assert tuple(a.shape) == tuple(b.shape) and raw(a) == raw(b), what
-
-
-def fingerprint(sw):
-    """Everything plan() promises to leave alone, as bytes."""
-    torch.cuda.synchronize()
-    recs, total = sw.episode_log()
-    return ([raw(sw.get_state(blk)) for blk in BLOCKS], raw(recs), total, sw.reset_error(), sw.launch_counts())
-
-
-def ground(sw, env=4):
-    """Drone 0 of `env` 1 cm above the ground: a MultiHover env crashes (z < 0.03) in step 0."""
-    st = sw.get_state(L.STATE_AGENT).clone()
-    st[L.F_POS + 2, env * sw.num_drones] = 0.01
-    sw.set_state(L.STATE_AGENT, st)
-
-
-def prepared(cfg, seed=3, warm=2, twins=0, grounded=False):
-    """`twins` + 1 swarms in the same mid-episode state."""
-    out = [QuadSwarm(**cfg) for _ in range(twins + 1)]
-    for sw in out:
-        sw.reset(seed)
-        for _ in range(warm):
-            sw.step(None)
-        if grounded:
-            ground(sw)
-    return out
-
-
-def random_nominal(pl, seed=11, scale=1.0):
-    """A nominal sequence of distinct values in (-scale, scale): candidate 0 equals no other candidate."""
-    gen = torch.Generator(device="cpu").manual_seed(seed)
-    return ((torch.rand(tuple(pl.nominal.shape), generator=gen) * 2 - 1) * scale).to(pl.nominal.device)
+BUFS = ("nominal", "candidates", "ret", "first_done", "weights", "best", "action", "tick")
 
 
 def restate(pl, lam, penalty):
@@ -129,18 +82,6 @@ def test_sample_copies_the_nominal_and_clips():
     assert int(pl.tick.item()) == 0          # sampling alone does not tick
     assert isinstance(pl, MPPIPlanner)
     sw.close()
-
-
-def ks_normal(x):
-    """One-sample KS against N(0, 1) at the 0.001 level, mean and variance within 4 standard errors."""
-    x = np.asarray(x, np.float64).ravel()
-    N = x.size
-    assert N >= 1 << 16
-    d = stats.kstest(x, "norm").statistic
-    print(f"N = {N}: KS {d:.5f} (critical {1.95 / np.sqrt(N):.5f}), mean {x.mean():+.5f}, var {x.var(ddof=1):.5f}")
-    assert d < 1.95 / np.sqrt(N)
-    assert abs(x.mean()) < 4 / np.sqrt(N)
-    assert abs(x.var(ddof=1) - 1) < 4 * np.sqrt(2 / (N - 1))
 
 
 def test_noise_is_standard_normal_a1():
@@ -354,20 +295,15 @@ def test_captured_tick_replays_what_eager_ticks_compute(cfg, C):
 
 
 # --------------------------------------------------------------------- 9. refusals
-def planner_bytes(pl):
-    torch.cuda.synchronize()
-    return [raw(t) for t in (pl.nominal, pl.candidates, pl.ret, pl.first_done, pl.weights, pl.best, pl.action, pl.tick)]
-
-
 def test_refusals_leave_swarm_and_planner_alone():
     sw = QuadSwarm(**c3(21))
     depth = sw.score_depth()
     pl = sw.mppi(depth, 3, 0.3, seed=4)               # creating a planner needs no reset
     pl.reset(random_nominal(pl))
-    held = planner_bytes(pl)
+    held = planner_bytes(pl, BUFS)
     with pytest.raises(L.QuadSwarmError, match="rc=-4.*qs_reset"):   # QS_E_STATE: plan before qs_reset
         pl.plan()
-    assert planner_bytes(pl) == held
+    assert planner_bytes(pl, BUFS) == held
     sw.reset(3)
     sw.step(None)
     before = fingerprint(sw)
@@ -383,7 +319,7 @@ def test_refusals_leave_swarm_and_planner_alone():
         sw.mppi(4, 3, (0.1, 0.2))                                 # one sigma per component, A = 1
     with pytest.raises(ValueError):
         pl.reset(torch.zeros((depth, 21, 8), device=sw.device))
-    assert fingerprint(sw) == before and planner_bytes(pl) == held
+    assert fingerprint(sw) == before and planner_bytes(pl, BUFS) == held
     pl.plan()                                                      # and the planner still works
     torch.cuda.synchronize()
     assert int(pl.tick.item()) == 1
