@@ -335,6 +335,32 @@ int qs_score_depth(const qs_handle* h);
 int qs_score(qs_handle* h, int n, int C, const float* const* actions,
              const qs_step_out* outs, const qs_score_out* score, void* stream);
 
+/* qs_score plus each drone's own share of the return.  (A new entry point of
+ * ABI 4, like qs_step_seq.)  ret_agent: device, [C][E][D] double, or NULL.
+ *
+ * MultiHover and Spiral form a step's env reward as the mean of D per-drone
+ * terms.  ret_agent[c][e][d] is the sum, in step order and in double, of drone
+ * d's term (in the handle's precision, widened) BEFORE the division by D, over
+ * steps 0..jd with jd as in qs_score_out.ret: the launch's own numbers, kept per
+ * lane and written once.
+ *
+ *  - ret_agent == NULL: the call is qs_score, in results and refusals.
+ *  - Every other output is, byte for byte, what qs_score writes; ret_agent is the
+ *    same bytes whatever else is requested.
+ *  - ret_agent counts as an output: it alone is something to write, and it may
+ *    not overlap an action buffer or another output (QS_E_INVALID).  C · E · D · 8
+ *    bytes past the 32-bit offsets: QS_E_INVALID.
+ *  - No mutation, depth, capture and the handles that cannot score: as qs_score.
+ *  - Scale.  ret[c][e] is about sum_d ret_agent[c][e][d] / D (the env reward
+ *    rounds the mean at every step), so a temperature or a penalty meant per
+ *    drone is on a scale D times the env-level one.
+ *  - Meaning.  A drone's term depends on its own actions alone only where drones
+ *    do not act on each other: with QS_AUX_DW (downwash) or PYB contacts another
+ *    drone's actions move it too, and weighting by ret_agent is an approximation. */
+int qs_score_agents(qs_handle* h, int n, int C, const float* const* actions,
+                    const qs_step_out* outs, const qs_score_out* score,
+                    double* ret_agent, void* stream);
+
 /* MPPI planner tick on top of qs_score: sample C candidate sequences round a
  * nominal one, score them from the handle's current state, and fold them back
  * into the nominal by their softmax weights, all on the device.  (New entry
@@ -383,7 +409,9 @@ typedef struct qs_mppi_spec {
   uint64_t seed;
 } qs_mppi_spec;
 
-typedef struct qs_mppi_bufs { /* device pointers owned by the planner           */
+typedef struct qs_mppi_bufs { /* device pointers owned by the planner; per-drone
+                                 mode (qs_pd_mppi_create): weights [C][E][D],
+                                 best [E][D]                                   */
   float* nominal;       /* [n][E][D][A]                                          */
   float* candidates;    /* [n][C][E][D][A]  (what qs_score reads)                */
   double* ret;          /* [C][E]  qs_score's ret                                */
@@ -474,7 +502,9 @@ typedef struct qs_cem_spec {
   uint64_t seed;
 } qs_cem_spec;
 
-typedef struct qs_cem_bufs {  /* device pointers owned by the planner           */
+typedef struct qs_cem_bufs {  /* device pointers owned by the planner; per-drone
+                                 mode (qs_pd_cem_create): elites [K][E][D],
+                                 iter_best [I][E][D]                           */
   float* mean;          /* [n][E][D][A]                                          */
   float* std;           /* [n][E][D][A]                                          */
   float* candidates;    /* [n][C][E][D][A]  (what qs_score reads)                */
@@ -498,6 +528,46 @@ int qs_cem_sample(qs_cem* p, int iteration, void* stream);
 int qs_cem_refit(qs_cem* p, int iteration, void* stream);
 int qs_cem_finish(qs_cem* p, void* stream);
 int qs_cem_plan(qs_cem* p, void* stream);
+
+/* Per-drone (factored) planner ticks.  qs_pd_mppi_create / qs_pd_cem_create take
+ * the same spec records and return the same planner types, driven by the same
+ * qs_mppi_* / qs_cem_* calls, in per-drone mode: every drone weighs (MPPI) or
+ * ranks (CEM) the same C candidates by its own return, so C candidates serve D
+ * searches at once.  (New entry points of ABI 4.)
+ *
+ * The semantics are the env-level ones above with agent (e, d) in the place of
+ * env e and the drone's A components in the place of the env's D · A:
+ *  - Score.  s[c][e][d] = ret_agent[c][e][d] - (first_done[c][e] < n ?
+ *    done_penalty : 0): the penalty comes from the env's first_done.
+ *  - Buffers.  The planner owns ret_agent [C][E][D] (qs_pd_*_ret_agent); weights
+ *    is [C][E][D], best [E][D], elites [K][E][D], iter_best [I][E][D].  ret and
+ *    first_done keep their shape and are still filled.
+ *  - MPPI.  best[e][d] = the lowest c of the largest s; w = softmax over c at
+ *    temperature lambda; new[j][e][d][a] = (float) sum_c w[c][e][d] ·
+ *    candidates[j][c][e][d][a], summed in double in the env-level order.  With
+ *    lambda = 0 the best candidate's [d][.] slice is copied bit for bit, so the
+ *    drones of one env may copy different candidates.  Shift, action and tick as
+ *    before.
+ *  - CEM.  Ranking (the same total order), the K elites, the two-pass refit,
+ *    alpha, sigma_min and iter_best per (e, d) over that drone's A components.
+ *  - Sampling is unchanged: the same Philox counters and the same bytes as the
+ *    env-level planner of the same spec, seed and tick; candidate 0 is the
+ *    nominal / mean for every drone.
+ *  - plan() scores with qs_score_agents(h, n, C, candidates, NULL, {ret,
+ *    first_done}, ret_agent, stream).  update / refit read candidates, ret_agent
+ *    and first_done as they are, so a caller may fill them itself.
+ *  - Scale.  ret is about sum_d ret_agent / D: a per-drone lambda or
+ *    done_penalty is on a scale D times the env-level one.
+ *  - Meaning.  Per-drone weighting is exact only where a drone's term depends on
+ *    its own actions; with QS_AUX_DW or contacts it is an approximation.
+ *  - Refusals (QS_E_INVALID, *out untouched): whatever qs_mppi_create /
+ *    qs_cem_create refuse, and C · E · D · 8 bytes of ret_agent or E · D · n
+ *    workgroups at 2^31 or more.  qs_pd_*_ret_agent on an env-level planner:
+ *    QS_E_INVALID.                                                              */
+int qs_pd_mppi_create(qs_handle* h, const qs_mppi_spec* spec, qs_mppi** out);
+int qs_pd_mppi_ret_agent(const qs_mppi* p, double** out);
+int qs_pd_cem_create(qs_handle* h, const qs_cem_spec* spec, qs_cem** out);
+int qs_pd_cem_ret_agent(const qs_cem* p, double** out);
 
 /* Multi-step launches this handle has made so far (host, no device work):
  * out[0] on the general multi-step kernel instances, out[1] on the

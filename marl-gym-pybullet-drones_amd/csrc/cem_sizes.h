@@ -53,6 +53,21 @@ inline bool cem_sizes(const CemShape& s, uint64_t b[kCemBufs]) {
   return true;
 }
 
+// Per-drone mode (qs_pd_cem_create): select and refit run over E · D "envs" with
+// rows of A components (mppi_pd_shape).  The shape their variant and grids are taken from:
+inline CemShape cem_pd_shape(const CemShape& s) { return CemShape{s.n, s.C, s.K, s.I, s.E * s.D, 1, s.A}; }
+// Bytes of every buffer in per-drone mode and of the planner's ret_agent: elites
+// grow to [K][E][D], iter_best to [I][E][D], the rest is cem_sizes'.  false where
+// cem_sizes or mppi_pd_sizes refuses the shape.
+inline bool cem_pd_sizes(const CemShape& s, uint64_t b[kCemBufs], uint64_t* ret_agent) {
+  uint64_t m[kMppiBufs];
+  if (!cem_sizes(s, b) || !mppi_pd_sizes(MppiShape{s.n, s.C, s.E, s.D, s.A}, m, ret_agent)) return false;
+  const uint64_t agents = (uint64_t)s.E * (uint64_t)s.D;        // < 2^27 (mppi_pd_sizes)
+  b[kCemElites] = (uint64_t)s.K * agents * 4u;                  // K <= 1024
+  b[kCemIterBest] = (uint64_t)s.I * agents * 8u;                // I <= 16
+  return true;
+}
+
 // Which select + refit runs.
 //  kCemPerThread: select by one thread per env that ranks every candidate by
 //    counting the candidates that come before it (C^2 comparisons a thread, reads

@@ -19,16 +19,20 @@ struct SigmaArg {
 };
 
 struct UpdateParams {
-  const float* cand;         // [n][C][E][D][A]
-  const double* ret;         // [C][E]
-  const int32_t* first_done; // [C][E]
+  // E counts the units that are weighed on their own and row their components:
+  // the envs and D · A, or in per-drone mode the E · D agents and A
+  // (planner_common.h, PlannerBase).  Either way [E][row] is [envs][D][A].
+  const float* cand;         // [n][C][E][row]
+  const double* ret;         // [C][E]: ret, or in per-drone mode ret_agent
+  const int32_t* first_done; // [C][E / fd_div]
   double* w;                 // [C][E]
   int32_t* best;             // [E]
-  float* nominal;            // [n][E][D][A]
-  float* action;             // [E][D][A]
+  float* nominal;            // [n][E][row]
+  float* action;             // [E][row]
   uint64_t* tick;
   double lambda, penalty;
-  int n, C, E, row, rowp;    // row = D · A, rowp = the power of two >= row
+  int n, C, E, row, rowp;    // rowp = the power of two >= row
+  int fd_div;                // 1, or in per-drone mode D
 };
 
 using qs::score_of;
@@ -181,7 +185,7 @@ namespace {
 UpdateParams update_params(const qs_mppi* p) {
   UpdateParams P;
   P.cand = (const float*)p->buf[qs::kMppiCandidates];
-  P.ret = (const double*)p->buf[qs::kMppiRet];
+  P.ret = p->scores(p->buf[qs::kMppiRet]);
   P.first_done = (const int32_t*)p->buf[qs::kMppiFirstDone];
   P.w = (double*)p->buf[qs::kMppiWeights];
   P.best = (int32_t*)p->buf[qs::kMppiBest];
@@ -190,9 +194,10 @@ UpdateParams update_params(const qs_mppi* p) {
   P.tick = (uint64_t*)p->buf[qs::kMppiTick];
   P.lambda = p->spec.lambda;
   P.penalty = p->spec.done_penalty;
-  P.n = p->n; P.C = p->C; P.E = p->E;
-  P.row = p->D * p->A;
+  P.n = p->n; P.C = p->C; P.E = p->units();
+  P.row = p->row();
   P.rowp = qs::mppi_row_pow2(P.row);
+  P.fd_div = p->fd_div();
   return P;
 }
 
@@ -231,24 +236,38 @@ int update_impl(qs_mppi* p, hipStream_t st) {
 
 }  // namespace
 
-extern "C" {
-
-int qs_mppi_create(qs_handle* h, const qs_mppi_spec* spec, qs_mppi** out) {
-  const char* who = "qs_mppi_create";
+namespace {
+int create_impl(const char* who, bool per_drone, qs_handle* h, const qs_mppi_spec* spec, qs_mppi** out) {
   qs_dims d;
   if (int rc = qs::planner_check_spec(who, "nominal", h, spec, out, &d)) return rc;
   if (!(spec->lambda >= 0.0) || !std::isfinite(spec->lambda))
-    return qs::set_last_error(QS_E_INVALID, "qs_mppi_create: lambda must be finite and >= 0 (0: greedy)");
+    return qs::set_last_error(QS_E_INVALID, std::string(who) + ": lambda must be finite and >= 0 (0: greedy)");
   qs_mppi* p = qs::planner_new<qs_mppi>(who, h, *spec, d);
   if (!p) return QS_E_NOMEM;
+  p->per_drone = per_drone;
   const qs::MppiShape shape{p->n, p->C, p->E, p->D, p->A};
-  if (!qs::mppi_sizes(shape, p->bytes)) return qs::planner_too_large(who, p);
-  p->variant = qs::mppi_variant(shape.E, shape.C, shape.D * shape.A);
-  p->grids = qs::mppi_grids(shape, p->variant);
+  if (per_drone ? !qs::mppi_pd_sizes(shape, p->bytes, &p->ret_agent_bytes) : !qs::mppi_sizes(shape, p->bytes))
+    return qs::planner_too_large(who, p);
+  const qs::MppiShape ushape = per_drone ? qs::mppi_pd_shape(shape) : shape;   // the update's units and rows
+  p->variant = qs::mppi_variant(ushape.E, ushape.C, ushape.D * ushape.A);
+  p->grids = qs::mppi_grids(ushape, p->variant);
   if (int rc = qs::planner_alloc(who, p, qs::kMppiCandidates)) return rc;
   *out = p;
   return QS_OK;
 }
+}  // namespace
+
+extern "C" {
+
+int qs_mppi_create(qs_handle* h, const qs_mppi_spec* spec, qs_mppi** out) {
+  return create_impl("qs_mppi_create", false, h, spec, out);
+}
+
+int qs_pd_mppi_create(qs_handle* h, const qs_mppi_spec* spec, qs_mppi** out) {
+  return create_impl("qs_pd_mppi_create", true, h, spec, out);
+}
+
+int qs_pd_mppi_ret_agent(const qs_mppi* p, double** out) { return qs::planner_ret_agent("qs_pd_mppi_ret_agent", p, out); }
 
 int qs_mppi_destroy(qs_mppi* p) { return qs::planner_destroy(p); }
 

@@ -23,23 +23,27 @@ struct StdMem {
   __device__ __forceinline__ float at(size_t i, int a) const { return std[i + a]; }
 };
 
+// In the select and refit records E counts the units that are ranked on their own
+// and row their components: the envs and D · A, or in per-drone mode the E · D
+// agents and A (planner_common.h, PlannerBase).  Either way [E][row] is [envs][D][A].
 struct SelectParams {
-  const double* ret;         // [C][E]
-  const int32_t* first_done; // [C][E]
+  const double* ret;         // [C][E]: ret, or in per-drone mode ret_agent
+  const int32_t* first_done; // [C][E / fd_div]
   int32_t* elites;           // [K][E]
   double* iter_best;         // [E]: this iteration's row
   double penalty;
   int n, C, K, E;
   int index_bytes;           // cem_index_bytes(C)
+  int fd_div;                // 1, or in per-drone mode D
 };
 
 struct RefitParams {
-  const float* cand;         // [n][C][E][D][A]
+  const float* cand;         // [n][C][E][row]
   const int32_t* elites;     // [K][E]
-  float* mean;               // [n][E][D][A]
-  float* std;                // [n][E][D][A]
+  float* mean;               // [n][E][row]
+  float* std;                // [n][E][row]
   double alpha;
-  int n, C, K, E, A, row, rowp;   // row = D · A, rowp = the power of two >= row
+  int n, C, K, E, A, row, rowp;   // rowp = the power of two >= row
   float sigma[4], sigma_min[4];
 };
 
@@ -340,13 +344,14 @@ int sample_impl(qs_cem* p, int iteration, hipStream_t st) {
 
 int refit_impl(qs_cem* p, int iteration, hipStream_t st) {
   SelectParams S;
-  S.ret = (const double*)p->buf[qs::kCemRet];
+  S.ret = p->scores(p->buf[qs::kCemRet]);
   S.first_done = (const int32_t*)p->buf[qs::kCemFirstDone];
   S.elites = (int32_t*)p->buf[qs::kCemElites];
-  S.iter_best = (double*)p->buf[qs::kCemIterBest] + (size_t)iteration * (size_t)p->E;
+  S.iter_best = (double*)p->buf[qs::kCemIterBest] + (size_t)iteration * (size_t)p->units();
   S.penalty = p->spec.done_penalty;
-  S.n = p->n; S.C = p->C; S.K = p->spec.elites; S.E = p->E;
+  S.n = p->n; S.C = p->C; S.K = p->spec.elites; S.E = p->units();
   S.index_bytes = qs::cem_index_bytes(p->C);
+  S.fd_div = p->fd_div();
   RefitParams R;
   R.cand = (const float*)p->buf[qs::kCemCandidates];
   R.elites = (const int32_t*)p->buf[qs::kCemElites];
@@ -354,7 +359,7 @@ int refit_impl(qs_cem* p, int iteration, hipStream_t st) {
   R.std = (float*)p->buf[qs::kCemStd];
   R.alpha = p->spec.alpha;
   R.n = S.n; R.C = S.C; R.K = S.K; R.E = S.E; R.A = p->A;
-  R.row = p->D * p->A;
+  R.row = p->row();
   R.rowp = qs::mppi_row_pow2(R.row);
   for (int a = 0; a < 4; ++a) { R.sigma[a] = p->spec.sigma[a]; R.sigma_min[a] = p->spec.sigma_min[a]; }
   if (p->variant == qs::kCemPerBlock) {
@@ -389,38 +394,53 @@ int bad_iteration(const qs_cem* p, int iteration, const char* who) {
 
 }  // namespace
 
-extern "C" {
-
-int qs_cem_create(qs_handle* h, const qs_cem_spec* spec, qs_cem** out) {
+namespace {
+int create_impl(const char* who, bool per_drone, qs_handle* h, const qs_cem_spec* spec, qs_cem** out) {
+  const std::string w = std::string(who) + ": ";
   using qs::set_last_error;
-  const char* who = "qs_cem_create";
   qs_dims d;
   if (int rc = qs::planner_check_spec(who, "mean", h, spec, out, &d)) return rc;
   if (spec->elites < 1 || spec->elites > spec->candidates || spec->elites > qs::kCemMaxElites)
-    return set_last_error(QS_E_INVALID, "qs_cem_create: elites = " + std::to_string(spec->elites) +
+    return set_last_error(QS_E_INVALID, w + "elites = " + std::to_string(spec->elites) +
                                             " is outside 1 .. min(candidates, " + std::to_string(qs::kCemMaxElites) + ")");
   if (spec->iterations < 1 || spec->iterations > qs::kCemMaxIterations)
-    return set_last_error(QS_E_INVALID, "qs_cem_create: iterations = " + std::to_string(spec->iterations) +
+    return set_last_error(QS_E_INVALID, w + "iterations = " + std::to_string(spec->iterations) +
                                             " is outside 1 .. " + std::to_string(qs::kCemMaxIterations));
   for (int a = 0; a < d.act_dim && a < 4; ++a) {
     if (!(spec->sigma_min[a] >= 0.0f) || !std::isfinite(spec->sigma_min[a]))
-      return set_last_error(QS_E_INVALID, "qs_cem_create: sigma_min[" + std::to_string(a) + "] must be finite and >= 0");
+      return set_last_error(QS_E_INVALID, w + "sigma_min[" + std::to_string(a) + "] must be finite and >= 0");
     if (spec->sigma_min[a] > spec->sigma[a])
-      return set_last_error(QS_E_INVALID, "qs_cem_create: sigma_min[" + std::to_string(a) + "] is above sigma[" +
+      return set_last_error(QS_E_INVALID, w + "sigma_min[" + std::to_string(a) + "] is above sigma[" +
                                               std::to_string(a) + "]");
   }
   if (!(spec->alpha >= 0.0) || !(spec->alpha < 1.0))
-    return set_last_error(QS_E_INVALID, "qs_cem_create: alpha must be in [0, 1)");
+    return set_last_error(QS_E_INVALID, w + "alpha must be in [0, 1)");
   qs_cem* p = qs::planner_new<qs_cem>(who, h, *spec, d);
   if (!p) return QS_E_NOMEM;
+  p->per_drone = per_drone;
   const qs::CemShape shape{p->n, p->C, spec->elites, spec->iterations, p->E, p->D, p->A};
-  if (!qs::cem_sizes(shape, p->bytes)) return qs::planner_too_large(who, p);
-  p->variant = qs::cem_variant(shape.E, shape.C, shape.D * shape.A);
-  p->grids = qs::cem_grids(shape, p->variant);
+  if (per_drone ? !qs::cem_pd_sizes(shape, p->bytes, &p->ret_agent_bytes) : !qs::cem_sizes(shape, p->bytes))
+    return qs::planner_too_large(who, p);
+  const qs::CemShape ushape = per_drone ? qs::cem_pd_shape(shape) : shape;   // the units and rows of select and refit
+  p->variant = qs::cem_variant(ushape.E, ushape.C, ushape.D * ushape.A);
+  p->grids = qs::cem_grids(ushape, p->variant);
   if (int rc = qs::planner_alloc(who, p, qs::kCemCandidates)) return rc;
   *out = p;
   return QS_OK;
 }
+}  // namespace
+
+extern "C" {
+
+int qs_cem_create(qs_handle* h, const qs_cem_spec* spec, qs_cem** out) {
+  return create_impl("qs_cem_create", false, h, spec, out);
+}
+
+int qs_pd_cem_create(qs_handle* h, const qs_cem_spec* spec, qs_cem** out) {
+  return create_impl("qs_pd_cem_create", true, h, spec, out);
+}
+
+int qs_pd_cem_ret_agent(const qs_cem* p, double** out) { return qs::planner_ret_agent("qs_pd_cem_ret_agent", p, out); }
 
 int qs_cem_destroy(qs_cem* p) { return qs::planner_destroy(p); }
 

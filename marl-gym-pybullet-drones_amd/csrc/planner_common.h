@@ -81,14 +81,19 @@ __global__ __launch_bounds__(kPlannerThreads) void planner_sample_kernel(SampleP
 }
 
 // A candidate's return, less the penalty where it ends an episode inside the n steps.
+// `ret` is [C][units] and ce = c · units + u; first_done is [C][units / fd_div]
+// and read at ce / fd_div.  Env-level planning has fd_div = 1 (a unit is an env);
+// per-drone planning has units = E · D agents and fd_div = D, so agent (e, d) of
+// candidate c reads ret_agent[c][e][d] and its env's first_done[c][e].
 __device__ __forceinline__ double penalised_score(const double* ret, const int32_t* first_done, int n, double penalty,
-                                                  size_t ce) {
-  return ret[ce] - (first_done[ce] < n ? penalty : 0.0);
+                                                  int fd_div, size_t ce) {
+  const size_t fd = fd_div == 1 ? ce : ce / (size_t)fd_div;
+  return ret[ce] - (first_done[fd] < n ? penalty : 0.0);
 }
-// ... from a kernel's parameter record that holds ret, first_done, n and penalty.
+// ... from a kernel's parameter record that holds ret, first_done, n, penalty and fd_div.
 template <class Params>
 __device__ __forceinline__ double score_of(const Params& P, size_t ce) {
-  return penalised_score(P.ret, P.first_done, P.n, P.penalty, ce);
+  return penalised_score(P.ret, P.first_done, P.n, P.penalty, P.fd_div, ce);
 }
 
 // The sums over a kPlannerBlockThreads workgroup of `acc` per component
@@ -123,6 +128,17 @@ struct PlannerBase {
   HandleInfo info;
   int n, C, E, D, A;
   std::vector<const float*> steps;   // candidates' n step pointers, the host array qs_score reads
+  // Per-drone mode (qs_pd_*_create): every drone weighs the candidates by its own
+  // return.  The update / refit kernels then run over E · D units with rows of A
+  // components, which is the memory they index anyway, and score a unit from
+  // ret_agent and its env's first_done.
+  bool per_drone = false;
+  void* ret_agent = nullptr;         // [C][E][D] doubles, per-drone mode only
+  uint64_t ret_agent_bytes = 0;
+  int units() const { return per_drone ? E * D : E; }      // what the kernels take for envs
+  int row() const { return per_drone ? A : D * A; }        // components of a unit's row
+  int fd_div() const { return per_drone ? D : 1; }         // units per entry of first_done
+  const double* scores(const void* ret) const { return (const double*)(per_drone ? ret_agent : ret); }
 };
 
 // The checks every planner spec goes through (`who`: the entry point, `centre`:
@@ -179,10 +195,12 @@ template <class T>
 void planner_free(T* p) {
   for (void* b : p->buf)
     if (b) (void)hipFree(b);
+  if (p->ret_agent) (void)hipFree(p->ret_agent);
 }
 
-// Allocates and zeroes every buffer of p->bytes and points `steps` into buffer
-// `candidates`; on failure frees what it made and deletes the record.
+// Allocates and zeroes every buffer of p->bytes (and ret_agent where
+// ret_agent_bytes is set) and points `steps` into buffer `candidates`; on failure
+// frees what it made and deletes the record.
 template <class T>
 int planner_alloc(const char* who, T* p, int candidates) {
   constexpr int kBufs = sizeof(p->buf) / sizeof(p->buf[0]);
@@ -190,6 +208,10 @@ int planner_alloc(const char* who, T* p, int candidates) {
   for (int i = 0; i < kBufs && e == hipSuccess; ++i) {
     e = hipMalloc(&p->buf[i], p->bytes[i]);
     if (e == hipSuccess) e = hipMemset(p->buf[i], 0, p->bytes[i]);
+  }
+  if (e == hipSuccess && p->ret_agent_bytes != 0) {
+    e = hipMalloc(&p->ret_agent, p->ret_agent_bytes);
+    if (e == hipSuccess) e = hipMemset(p->ret_agent, 0, p->ret_agent_bytes);
   }
   if (e != hipSuccess) {
     planner_free(p);
@@ -229,10 +251,23 @@ inline int planner_ready(const char* who, PlannerBase* p) {
   return QS_OK;
 }
 
-// Scores the candidates from the handle's current state into ret / first_done.
+// Scores the candidates from the handle's current state into ret / first_done
+// (and, in per-drone mode, ret_agent).
 inline int planner_score(PlannerBase* p, void* ret, void* first_done, void* stream) {
   const qs_score_out so{ret, (int32_t*)first_done};
+  if (p->per_drone)
+    return qs_score_agents(p->h, p->n, p->C, p->steps.data(), nullptr, &so, (double*)p->ret_agent, stream);
   return qs_score(p->h, p->n, p->C, p->steps.data(), nullptr, &so, stream);
+}
+
+// qs_pd_*_ret_agent.
+inline int planner_ret_agent(const char* who, const PlannerBase* p, double** out) {
+  if (!p || !out) return set_last_error(QS_E_INVALID, std::string(who) + ": null argument");
+  if (!p->per_drone)
+    return set_last_error(QS_E_INVALID, std::string(who) + ": this is an env-level planner (it has no ret_agent; "
+                                                           "create it with the qs_pd_ entry point)");
+  *out = (double*)p->ret_agent;
+  return QS_OK;
 }
 
 }  // namespace qs

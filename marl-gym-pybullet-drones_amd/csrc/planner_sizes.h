@@ -6,6 +6,8 @@
 // arithmetic and live here: how many bytes each buffer takes and whether the
 // shape is one qs_score (and the sample kernel's Philox counter) can take, which
 // of the two reduction variants the update runs, and the grids of the launches.
+// A planner in per-drone mode (qs_pd_mppi_create) has the same buffers with a drone
+// axis on weights and best, plus ret_agent: mppi_pd_shape and mppi_pd_sizes below.
 #pragma once
 
 #include <cstddef>
@@ -57,6 +59,29 @@ inline bool mppi_sizes(const MppiShape& s, uint64_t b[kMppiBufs]) {
   b[kMppiBest] = (uint64_t)s.E * 4u;
   b[kMppiAction] = (uint64_t)s.E * row * 4u;
   b[kMppiTick] = 8u;
+  return true;
+}
+
+// Per-drone mode (qs_pd_mppi_create): the update treats agent (e, d) as env-level
+// planning treats env e, so it runs over E · D "envs" with rows of A components
+// and the same memory.  The shape the variant and the update's grids are taken from:
+inline MppiShape mppi_pd_shape(const MppiShape& s) { return MppiShape{s.n, s.C, s.E * s.D, 1, s.A}; }
+// Bytes of every buffer in per-drone mode and of the planner's ret_agent
+// ([C][E][D] doubles): weights grow to [C][E][D], best to [E][D], the rest is
+// mppi_sizes'.  false where mppi_sizes refuses the shape, where ret_agent would
+// pass the 32-bit offsets of qs_score_agents (C · E · D · 8 bytes below 2^31), or
+// where the update's workgroup-per-(agent, step) grid would pass 2^31.  Every
+// product is formed in 64 bits from factors mppi_sizes has bounded.
+inline bool mppi_pd_sizes(const MppiShape& s, uint64_t b[kMppiBufs], uint64_t* ret_agent) {
+  if (!mppi_sizes(s, b)) return false;                          // C · E · D < 2^31, n <= 32
+  const uint64_t lim = uint64_t(1) << 31;
+  const uint64_t agents = (uint64_t)s.E * (uint64_t)s.D;        // < 2^31 (C >= 2)
+  const uint64_t N = (uint64_t)s.C * agents;                    // < 2^31
+  if (N * 8u >= lim) return false;
+  if ((uint64_t)s.n * agents >= lim) return false;              // n <= 32
+  b[kMppiWeights] = N * 8u;
+  b[kMppiBest] = agents * 4u;
+  *ret_agent = N * 8u;
   return true;
 }
 

@@ -716,13 +716,16 @@ static int score_depth(const qs_handle* h) {
   return qs::score_depth(kSeqLdsMax, kLdsStatic + kLdsGrain, image, plan - hist, h->dims.act_dim);
 }
 
-template <class T> static int score_impl(qs_handle* h, int n, int C, const float* const* actions, const qs_step_out* outs,
-                                         const qs_score_out* score, hipStream_t st) {
+// `who`: the entry point, qs_score or qs_score_agents; ret_agent: the latter's extra output, or null.
+template <class T> static int score_impl(const char* who_c, qs_handle* h, int n, int C, const float* const* actions,
+                                         const qs_step_out* outs, const qs_score_out* score, double* ret_agent,
+                                         hipStream_t st) {
+  const std::string who = std::string(who_c) + ": ";
   const qs_dims& d = h->dims;
   uint64_t bytes[qs::kScoreOuts], act_bytes = 0;
   const qs::ScoreShape shape{C, d.num_envs, d.num_drones, d.obs_dim, d.act_dim, d.precision};
   if (!qs::score_sizes(shape, bytes, &act_bytes) || !qs::score_fits(act_bytes))
-    return fail(QS_E_INVALID, "qs_score: C * num_envs * num_drones is too large for one launch (32-bit offsets)");
+    return fail(QS_E_INVALID, who + "C * num_envs * num_drones is too large for one launch (32-bit offsets)");
   qs::ScoreRanges ranges;
   bool any_out = false, room = true;
   const char* const names[qs::kScoreOuts] = {"obs", "reward", "terminated", "truncated", "terminal_obs", "reasons",
@@ -740,15 +743,22 @@ template <class T> static int score_impl(qs_handle* h, int n, int C, const float
     const qs::FuseOuts fo = to_outs(outs[j]);
     for (int i = 0; i < qs::kFuseOuts; ++i)
       if (!add_out(fo.p[i], i))
-        return fail(QS_E_INVALID, std::string("qs_score: ") + names[i] + " of C * num_envs envs is too large (32-bit offsets)");
+        return fail(QS_E_INVALID, who + names[i] + " of C * num_envs envs is too large (32-bit offsets)");
   }
   if (score) {
     if (!add_out(score->ret, 7) || !add_out(score->first_done, 8))
-      return fail(QS_E_INVALID, "qs_score: C * num_envs is too large (32-bit offsets)");
+      return fail(QS_E_INVALID, who + "C * num_envs is too large (32-bit offsets)");
   }
-  if (!any_out) return fail(QS_E_INVALID, "qs_score: nothing to write (no output in outs[] and neither ret nor first_done)");
+  if (ret_agent) {
+    any_out = true;
+    const uint64_t ab = qs::score_agent_bytes(shape);
+    if (!qs::score_fits(ab))
+      return fail(QS_E_INVALID, who + "ret_agent of C * num_envs * num_drones doubles is too large (32-bit offsets)");
+    room = ranges.add(ret_agent, ab, false) && room;
+  }
+  if (!any_out) return fail(QS_E_INVALID, who + "nothing to write (no output in outs[] and neither ret nor first_done)");
   if (!room || ranges.overlap())
-    return fail(QS_E_INVALID, "qs_score: an output overlaps another output or an action buffer");
+    return fail(QS_E_INVALID, who + "an output overlaps another output or an action buffer");
   qs::ParamsScore<T> P;
   std::memset(&P, 0, sizeof(P));
   fill_params(h, P);
@@ -763,6 +773,7 @@ template <class T> static int score_impl(qs_handle* h, int n, int C, const float
     P.act[j] = actions[j];
   }
   if (score) { P.ret = (double*)score->ret; P.first_done = score->first_done; }
+  P.ret_agent = ret_agent;
   return launch_kernel<T, 3>(h, P, st, nullptr, false);
 }
 
@@ -1058,24 +1069,36 @@ int qs_step_seq(qs_handle* h, int n, const float* const* actions, const qs_step_
 
 int qs_score_depth(const qs_handle* h) { return h ? score_depth(h) : 0; }
 
-int qs_score(qs_handle* h, int n, int C, const float* const* actions, const qs_step_out* outs, const qs_score_out* score,
-             void* stream) {
-  if (!h) return fail(QS_E_INVALID, "qs_score: null handle");
-  if (const char* why = score_refusal(h)) return fail(QS_E_INVALID, std::string("qs_score: this handle cannot score: ") + why);
+// qs_score and qs_score_agents (ret_agent null: the same call under the other name).
+static int score_entry(const char* who_c, qs_handle* h, int n, int C, const float* const* actions, const qs_step_out* outs,
+                       const qs_score_out* score, double* ret_agent, void* stream) {
+  const std::string who = std::string(who_c) + ": ";
+  if (!h) return fail(QS_E_INVALID, who + "null handle");
+  if (const char* why = score_refusal(h)) return fail(QS_E_INVALID, who + "this handle cannot score: " + why);
   const int depth = score_depth(h);
-  if (depth < 1) return fail(QS_E_INVALID, "qs_score: this handle cannot score: no step's action rows fit in LDS");
-  if (C < 1) return fail(QS_E_INVALID, "qs_score: C must be >= 1");
+  if (depth < 1) return fail(QS_E_INVALID, who + "this handle cannot score: no step's action rows fit in LDS");
+  if (C < 1) return fail(QS_E_INVALID, who + "C must be >= 1");
   if (n < 1 || n > depth)
-    return fail(QS_E_INVALID, "qs_score: n = " + std::to_string(n) + " is outside 1 .. qs_score_depth = " +
+    return fail(QS_E_INVALID, who + "n = " + std::to_string(n) + " is outside 1 .. qs_score_depth = " +
                                   std::to_string(depth) + " (longer horizons are not cut into several launches)");
-  if (!actions) return fail(QS_E_INVALID, "qs_score: actions is null");
+  if (!actions) return fail(QS_E_INVALID, who + "actions is null");
   for (int j = 0; j < n; ++j)
-    if (!actions[j]) return fail(QS_E_INVALID, "qs_score: actions[" + std::to_string(j) + "] is null");
-  if (!h->reset_done) return fail(QS_E_STATE, "qs_score: call qs_reset first");
+    if (!actions[j]) return fail(QS_E_INVALID, who + "actions[" + std::to_string(j) + "] is null");
+  if (!h->reset_done) return fail(QS_E_STATE, who + "call qs_reset first");
   h->fuse.forget();
   hipStream_t st = (hipStream_t)stream;
-  if (h->dims.precision == 8) return score_impl<double>(h, n, C, actions, outs, score, st);
-  return score_impl<float>(h, n, C, actions, outs, score, st);
+  if (h->dims.precision == 8) return score_impl<double>(who_c, h, n, C, actions, outs, score, ret_agent, st);
+  return score_impl<float>(who_c, h, n, C, actions, outs, score, ret_agent, st);
+}
+
+int qs_score(qs_handle* h, int n, int C, const float* const* actions, const qs_step_out* outs, const qs_score_out* score,
+             void* stream) {
+  return score_entry("qs_score", h, n, C, actions, outs, score, nullptr, stream);
+}
+
+int qs_score_agents(qs_handle* h, int n, int C, const float* const* actions, const qs_step_out* outs,
+                    const qs_score_out* score, double* ret_agent, void* stream) {
+  return score_entry("qs_score_agents", h, n, C, actions, outs, score, ret_agent, stream);
 }
 
 // qs_state_io's view of the per-env records: counters as [QS_ENV_FIELDS][E]

@@ -320,6 +320,7 @@ template <class T> struct ParamsScore : ParamsSeq<T> {
   int store_state;       // always 0: nothing is stored to the handle (see the end of step_kernel for why it exists)
   double* ret;           // [E] or NULL: the candidate's return up to its first done
   int32_t* first_done;   // [E] or NULL: that step, nsteps if none
+  double* ret_agent;     // [E][D] or NULL: each drone's own reward terms (before the division by D) up to that step
 };
 // Arguments of the ring instances (step_kernel HOT = 2): nsteps may exceed
 // kMaxFuse, step k of the launch writes io[k mod period] (step_fuse.h, can_wrap).
@@ -1123,6 +1124,10 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
   // step order in double, and that step (−1: not done yet)
   [[maybe_unused]] double score_ret = 0;
   [[maybe_unused]] int score_fd = -1;
+  // FUSE = 3 (every lane): this drone's own terms of those rewards, summed likewise,
+  // while its env has not ended
+  [[maybe_unused]] double score_agent = 0;
+  [[maybe_unused]] bool score_live = true;
 
   float cur_act[A];            // this step's action (newest history entry)
 #pragma unroll
@@ -1834,6 +1839,12 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
       __syncthreads();
       done_env = valid && s.done[lenv];
     }
+    if constexpr (kScore) {   // the drone's term of this step's reward, up to and including the env's first done step
+      if (score_live) {
+        score_agent += (double)rterm;
+        score_live = !done_env;
+      }
+    }
   } else if (mode == MODE_RESET_ALL) {
     wait_vm0();
     // qs_reset: every env starts episode 0 (history is zero after qs_reset)
@@ -2164,6 +2175,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
       if (P.ret) P.ret[e] = score_ret;
       if (P.first_done) P.first_done[e] = score_fd < 0 ? launch_steps(P) : score_fd;
     }
+    if (valid && P.ret_agent) P.ret_agent[a] = score_agent;   // a < C · E · D < 2^31 (step_score.h)
   }
   // ---------------- per-env records: staged in LDS, stored as one span
   if constexpr (!kScore) {

@@ -57,6 +57,11 @@ inline bool score_sizes(const ScoreShape& s, uint64_t b[kScoreOuts], uint64_t* a
   *act = b[6];
   return true;
 }
+// Bytes of qs_score_agents' ret_agent, [C][E][D] doubles, of a shape score_sizes
+// accepted (C · E · D < 2^31, so the product stays far inside 64 bits).
+inline uint64_t score_agent_bytes(const ScoreShape& s) {
+  return (uint64_t)s.C * (uint64_t)s.E * (uint64_t)s.D * 8u;
+}
 // A buffer the kernel may address: its byte offsets fit 32 bits with room to spare.
 inline bool score_fits(uint64_t bytes) { return bytes < (uint64_t(1) << 31); }
 
@@ -67,7 +72,7 @@ struct ScoreRange {
   uintptr_t lo, hi;   // [lo, hi)
   bool action;
 };
-constexpr int kScoreMaxRanges = kScoreMaxSteps * (kScoreStepOuts + 1) + 2;
+constexpr int kScoreMaxRanges = kScoreMaxSteps * (kScoreStepOuts + 1) + 3;   // … ret, first_done and ret_agent
 struct ScoreRanges {
   ScoreRange r[kScoreMaxRanges];
   int n = 0;

@@ -275,7 +275,7 @@ class QuadSwarm:
 
     _SCORE_OUTS = ("obs", "reward", "terminated", "truncated", "terminal_obs", "reasons", "actions_out")
 
-    def score(self, actions, outs=None, *, ret=None, first_done=None):
+    def score(self, actions, outs=None, *, ret=None, first_done=None, ret_agent=None):
         """Run C candidate action sequences of n steps each from the swarm's current
         state in one launch, and leave the swarm exactly as it was (qs_score): no
         state, history, episode log or counter changes.  Virtual env (c, e) starts
@@ -289,8 +289,10 @@ class QuadSwarm:
         reward (C, E), ...); an output that is not named is not written.  ret:
         (C, E) float64, the rewards of steps 0 .. the candidate's first done step
         (all n if none), summed in step order; first_done: (C, E) int32, that step,
-        or n.  At least one output must be named, none may overlap another or an
-        action tensor, and 1 <= n <= score_depth()."""
+        or n.  ret_agent: (C, E, D) float64, each drone's own terms of those rewards
+        before the division by D, summed over the same steps (qs_score_agents): ret
+        is about ret_agent.sum(-1) / D.  At least one output must be named, none may
+        overlap another or an action tensor, and 1 <= n <= score_depth()."""
         E, D, A, O = self.num_envs, self.num_drones, self.act_dim, self.obs_dim
         if isinstance(actions, torch.Tensor):
             if actions.dim() != 5:
@@ -309,7 +311,7 @@ class QuadSwarm:
         want = dict(obs=(torch.float32, C * E * D * O), reward=(self.rdtype, C * E), terminated=(torch.uint8, C * E),
                     truncated=(torch.uint8, C * E), terminal_obs=(torch.float32, C * E * D * O),
                     reasons=(torch.uint8, C * E * D), actions_out=(torch.float32, C * E * D * A),
-                    ret=(torch.float64, C * E), first_done=(torch.int32, C * E))
+                    ret=(torch.float64, C * E), first_done=(torch.int32, C * E), ret_agent=(torch.float64, C * E * D))
 
         def buf(t, what):
             if t is None:
@@ -335,30 +337,40 @@ class QuadSwarm:
         if ret is not None or first_done is not None:
             so = ctypes.byref(L.QsScoreOut(buf(ret, "ret"), buf(first_done, "first_done")))
         ptrs = (ctypes.c_void_p * n)(*[a.data_ptr() for a in acts])
-        L.check(self.lib.qs_score(self._h, n, C, ptrs, arr, so, self._stream()), "qs_score")
+        if ret_agent is None:
+            L.check(self.lib.qs_score(self._h, n, C, ptrs, arr, so, self._stream()), "qs_score")
+            return
+        if not hasattr(self.lib, "qs_score_agents"):
+            raise L.QuadSwarmError(f"{L.LIB_PATH} has no qs_score_agents: rebuild the HIP extension")
+        L.check(self.lib.qs_score_agents(self._h, n, C, ptrs, arr, so, buf(ret_agent, "ret_agent"), self._stream()),
+                "qs_score_agents")
 
-    def mppi(self, horizon, candidates, sigma, lo=-1.0, hi=1.0, lam=1.0, done_penalty=0.0, seed=0):
+    def mppi(self, horizon, candidates, sigma, lo=-1.0, hi=1.0, lam=1.0, done_penalty=0.0, seed=0, per_drone=False):
         """An `MPPIPlanner` on this swarm (qs_mppi_create): `candidates` action
         sequences of `horizon` steps (1 .. score_depth()) are drawn round a nominal
         one with per-component noise `sigma` (a number or one per action component),
         clipped to [lo, hi], scored from the swarm's current state and folded back
         by their softmax weights at temperature `lam` (0: the best one wins);
-        `done_penalty` is taken off a candidate that ends an episode."""
-        planner = MPPIPlanner(self, horizon, candidates, sigma, lo, hi, lam, done_penalty, seed)
+        `done_penalty` is taken off a candidate that ends an episode.  per_drone=True
+        (qs_pd_mppi_create): every drone weighs the candidates by its own return
+        (`MPPIPlanner`)."""
+        planner = MPPIPlanner(self, horizon, candidates, sigma, lo, hi, lam, done_penalty, seed, per_drone)
         self.__dict__.setdefault("_planners", weakref.WeakSet()).add(planner)   # close() ends them first
         return planner
 
     def cem(self, horizon, candidates, elites, sigma, iterations=3, lo=-1.0, hi=1.0, alpha=0.0, sigma_min=0.0,
-            done_penalty=0.0, seed=0):
+            done_penalty=0.0, seed=0, per_drone=False):
         """A `CEMPlanner` on this swarm (qs_cem_create): per tick and env,
         `iterations` rounds of drawing `candidates` action sequences of `horizon`
         steps (1 .. score_depth()) round a mean with a per-element spread (started
         from `sigma` at every tick: a number or one per action component), clipped
         to [lo, hi], scoring them from the swarm's current state and refitting mean
         and spread to the `elites` best, smoothed by `alpha` and floored at
-        `sigma_min`; `done_penalty` is taken off a candidate that ends an episode."""
+        `sigma_min`; `done_penalty` is taken off a candidate that ends an episode.
+        per_drone=True (qs_pd_cem_create): every drone ranks the candidates by its own
+        return (`CEMPlanner`)."""
         planner = CEMPlanner(self, horizon, candidates, elites, sigma, iterations, lo, hi, alpha, sigma_min,
-                             done_penalty, seed)
+                             done_penalty, seed, per_drone)
         self.__dict__.setdefault("_planners", weakref.WeakSet()).add(planner)   # close() ends them first
         return planner
 
@@ -434,11 +446,19 @@ class _Planner:
     points `<_PREFIX>_*`, the device views, `plan`, `step_t` and `close`."""
 
     _PREFIX = None   # "qs_mppi" / "qs_cem"
+    per_drone = False
+    ret_agent = None   # per-drone mode: the (C, E, D) float64 view of the planner's ret_agent
 
-    def _bind(self, swarm):
-        self.swarm, self.lib = swarm, swarm.lib
-        if not hasattr(self.lib, f"{self._PREFIX}_create"):
-            raise L.QuadSwarmError(f"{L.LIB_PATH} has no {self._PREFIX}_create: rebuild the HIP extension")
+    def _bind(self, swarm, per_drone=False):
+        self.swarm, self.lib, self.per_drone = swarm, swarm.lib, bool(per_drone)
+        self._create_fn = f"{self._PREFIX.replace('qs_', 'qs_pd_') if self.per_drone else self._PREFIX}_create"
+        if not hasattr(self.lib, self._create_fn):
+            raise L.QuadSwarmError(f"{L.LIB_PATH} has no {self._create_fn}: rebuild the HIP extension")
+
+    def _units(self):
+        """The leading shape of what is weighed on its own: (E,), or (E, D) in per-drone mode."""
+        sw = self.swarm
+        return (sw.num_envs, sw.num_drones) if self.per_drone else (sw.num_envs,)
 
     def _per_component(self, v, what):
         A = self.swarm.act_dim
@@ -459,11 +479,15 @@ class _Planner:
         self._p = ctypes.c_void_p()
         self._stepper = swarm.step   # what step_t runs the action with (SwarmVecEnv.mppi / .cem: its step_t)
         with torch.cuda.device(swarm.device):
-            L.check(getattr(self.lib, f"{self._PREFIX}_create")(swarm._h, ctypes.byref(spec), ctypes.byref(self._p)),
-                    f"{self._PREFIX}_create")
+            L.check(getattr(self.lib, self._create_fn)(swarm._h, ctypes.byref(spec), ctypes.byref(self._p)), self._create_fn)
         L.check(getattr(self.lib, f"{self._PREFIX}_buffers")(self._p, ctypes.byref(bufs)), f"{self._PREFIX}_buffers")
         for name, shape, typestr in views:
             setattr(self, name, torch.as_tensor(_DeviceSpan(getattr(bufs, name), shape, typestr), device=swarm.device))
+        if self.per_drone:
+            fn, ra = self._create_fn.replace("_create", "_ret_agent"), ctypes.c_void_p()
+            L.check(getattr(self.lib, fn)(self._p, ctypes.byref(ra)), fn)
+            shape = (spec.candidates, swarm.num_envs, swarm.num_drones)
+            self.ret_agent = torch.as_tensor(_DeviceSpan(ra.value, shape, "<f8"), device=swarm.device)
 
     def _stream(self):
         return self.swarm._stream()
@@ -516,12 +540,21 @@ class MPPIPlanner(_Planner):
     copies; they dangle after `close()`): nominal (n, E, D, A), candidates
     (n, C, E, D, A), ret (C, E) float64, first_done (C, E) int32, weights (C, E)
     float64, best (E,) int32, action (E, D, A), tick (1,) (the uint64 counter,
-    viewed as int64).  The swarm must outlive the planner."""
+    viewed as int64).  The swarm must outlive the planner.
+
+    per_drone=True (qs_pd_mppi_create): every drone weighs the candidates by its
+    own return, `ret_agent` (C, E, D) float64, less `done_penalty` where its env
+    ends; weights is then (C, E, D) and best (E, D), and with lam = 0 each drone
+    copies its own best candidate's slice.  ret is about ret_agent.sum(-1) / D, so
+    a per-drone `lam` or `done_penalty` is on a scale D times the env-level one;
+    with downwash or contacts a drone's return also depends on the others'
+    actions and the factored weighting is an approximation."""
 
     _PREFIX = "qs_mppi"
 
-    def __init__(self, swarm, horizon, candidates, sigma, lo=-1.0, hi=1.0, lam=1.0, done_penalty=0.0, seed=0):
-        self._bind(swarm)
+    def __init__(self, swarm, horizon, candidates, sigma, lo=-1.0, hi=1.0, lam=1.0, done_penalty=0.0, seed=0,
+                 per_drone=False):
+        self._bind(swarm, per_drone)
         sig = self._per_component(sigma, "sigma")
         spec = L.QsMppiSpec()
         spec.horizon, spec.candidates = int(horizon), int(candidates)
@@ -533,7 +566,7 @@ class MPPIPlanner(_Planner):
         n, C, E, D, A = self.horizon, self.num_candidates, swarm.num_envs, swarm.num_drones, swarm.act_dim
         self._create(spec, L.QsMppiBufs(), (
             ("nominal", (n, E, D, A), "<f4"), ("candidates", (n, C, E, D, A), "<f4"), ("ret", (C, E), "<f8"),
-            ("first_done", (C, E), "<i4"), ("weights", (C, E), "<f8"), ("best", (E,), "<i4"),
+            ("first_done", (C, E), "<i4"), ("weights", (C,) + self._units(), "<f8"), ("best", self._units(), "<i4"),
             ("action", (E, D, A), "<f4"), ("tick", (1,), "<i8")))
 
     def reset(self, nominal=None):
@@ -564,13 +597,18 @@ class CEMPlanner(_Planner):
     copies; they dangle after `close()`): mean and std (n, E, D, A), candidates
     (n, C, E, D, A), ret (C, E) float64, first_done (C, E) int32, elites (K, E)
     int32, iter_best (I, E) float64, action (E, D, A), tick (1,) (the uint64
-    counter, viewed as int64).  The swarm must outlive the planner."""
+    counter, viewed as int64).  The swarm must outlive the planner.
+
+    per_drone=True (qs_pd_cem_create): every drone ranks the candidates by its own
+    return, `ret_agent` (C, E, D) float64, less `done_penalty` where its env ends,
+    and refits its own A components; elites is then (K, E, D) and iter_best
+    (I, E, D).  The scale and the caveat are `MPPIPlanner`'s."""
 
     _PREFIX = "qs_cem"
 
     def __init__(self, swarm, horizon, candidates, elites, sigma, iterations=3, lo=-1.0, hi=1.0, alpha=0.0,
-                 sigma_min=0.0, done_penalty=0.0, seed=0):
-        self._bind(swarm)
+                 sigma_min=0.0, done_penalty=0.0, seed=0, per_drone=False):
+        self._bind(swarm, per_drone)
         sig, smin = self._per_component(sigma, "sigma"), self._per_component(sigma_min, "sigma_min")
         spec = L.QsCemSpec()
         spec.horizon, spec.candidates, spec.elites, spec.iterations = int(horizon), int(candidates), int(elites), int(iterations)
@@ -584,8 +622,8 @@ class CEMPlanner(_Planner):
         E, D, A = swarm.num_envs, swarm.num_drones, swarm.act_dim
         self._create(spec, L.QsCemBufs(), (
             ("mean", (n, E, D, A), "<f4"), ("std", (n, E, D, A), "<f4"), ("candidates", (n, C, E, D, A), "<f4"),
-            ("ret", (C, E), "<f8"), ("first_done", (C, E), "<i4"), ("elites", (K, E), "<i4"),
-            ("iter_best", (I, E), "<f8"), ("action", (E, D, A), "<f4"), ("tick", (1,), "<i8")))
+            ("ret", (C, E), "<f8"), ("first_done", (C, E), "<i4"), ("elites", (K,) + self._units(), "<i4"),
+            ("iter_best", (I,) + self._units(), "<f8"), ("action", (E, D, A), "<f4"), ("tick", (1,), "<i8")))
 
     def reset(self, mean=None):
         """Set the mean sequence ((n, E, D, A) float32 on the device; None: zeros) and tick = 0."""

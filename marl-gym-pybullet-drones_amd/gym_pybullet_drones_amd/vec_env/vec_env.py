@@ -106,7 +106,7 @@ class SwarmVecEnv(VecEnv):
         super().__init__(num_envs, observation_space_for(self.swarm), action_space_for(self.swarm))
         self._actions = None
         self._rollout_bufs = {}   # rollout_t's output buffers, by step count
-        self._score_bufs = {}     # score_t's, by (steps, candidates, per_step)
+        self._score_bufs = {}     # score_t's, by (steps, candidates, per_step, per_drone)
         self.NUM_DRONES = self.swarm.num_drones
         self.CTRL_FREQ = self.swarm.ctrl_freq
         self.CTRL_TIMESTEP = 1.0 / self.CTRL_FREQ
@@ -194,13 +194,16 @@ class SwarmVecEnv(VecEnv):
         sw.step_many([{k: v[j] for k, v in out.items()} for j in range(n)], actions=actions)
         return out["obs"], out["reward"], out["terminated"], out["truncated"]
 
-    def score_t(self, actions, per_step=False):
+    def score_t(self, actions, per_step=False, per_drone=False):
         """Score C candidate action sequences from the envs' current state without
         stepping them (QuadSwarm.score): `actions` is a (n, C, E, D, A) device
         tensor.  Returns (ret (C, E) float64, first_done (C, E) int32): candidate
         c's reward summed over its steps up to env e's first done step, and that
         step (n if the env was never done).  per_step=True: also the stacked
-        (reward, terminated, truncated), each (n, C, E).  One launch, no host sync;
+        (reward, terminated, truncated), each (n, C, E).  per_drone=True: also, last
+        in the tuple, ret_agent (C, E, D) float64: each drone's own terms of those
+        rewards before the division by D, summed over the same steps
+        (QuadSwarm.score's ret_agent).  One launch, no host sync;
         the episode log, the counters and the state are untouched.  The buffers
         are allocated once per shape and returned again by every later call of
         that shape."""
@@ -208,7 +211,7 @@ class SwarmVecEnv(VecEnv):
         if actions.dim() != 5:
             raise ValueError(f"actions must be a (n, C, {sw.num_envs}, {sw.num_drones}, {sw.act_dim}) tensor")
         n, C = actions.shape[0], actions.shape[1]
-        key = (n, C, bool(per_step))
+        key = (n, C, bool(per_step), bool(per_drone))
         own = self._score_bufs.get(key)
         if own is None:
             kw = dict(device=sw.device)
@@ -218,17 +221,23 @@ class SwarmVecEnv(VecEnv):
                 own.update(reward=torch.zeros((n, C, sw.num_envs), dtype=sw.rdtype, **kw),
                            terminated=torch.zeros((n, C, sw.num_envs), dtype=torch.uint8, **kw),
                            truncated=torch.zeros((n, C, sw.num_envs), dtype=torch.uint8, **kw))
+            if per_drone:
+                own.update(ret_agent=torch.zeros((C, sw.num_envs, sw.num_drones), dtype=torch.float64, **kw))
             self._score_bufs[key] = own
         outs = None
         if per_step:
             outs = [{k: own[k][j] for k in ("reward", "terminated", "truncated")} for j in range(n)]
-        sw.score(actions, outs, ret=own["ret"], first_done=own["first_done"])
+        sw.score(actions, outs, ret=own["ret"], first_done=own["first_done"], ret_agent=own.get("ret_agent"))
+        res = (own["ret"], own["first_done"])
         if per_step:
-            return own["ret"], own["first_done"], own["reward"], own["terminated"], own["truncated"]
-        return own["ret"], own["first_done"]
+            res += (own["reward"], own["terminated"], own["truncated"])
+        if per_drone:
+            res += (own["ret_agent"],)
+        return res
 
     def mppi(self, horizon, candidates, sigma, **kw):
-        """An `MPPIPlanner` on these envs (QuadSwarm.mppi, same arguments).  Its
+        """An `MPPIPlanner` on these envs (QuadSwarm.mppi, same arguments, `per_drone`
+        among them).  Its
         `step_t(**bufs)` is one receding-horizon tick: `plan()` from the envs'
         current state, then `step_t(planner.action, **bufs)`, with step_t's
         return; a few launches on the current stream, no host sync."""
@@ -237,7 +246,8 @@ class SwarmVecEnv(VecEnv):
         return planner
 
     def cem(self, horizon, candidates, elites, sigma, **kw):
-        """A `CEMPlanner` on these envs (QuadSwarm.cem, same arguments).  Its
+        """A `CEMPlanner` on these envs (QuadSwarm.cem, same arguments, `per_drone`
+        among them).  Its
         `step_t(**bufs)` is one receding-horizon tick: `plan()` from the envs'
         current state, then `step_t(planner.action, **bufs)`, with step_t's
         return; launches on the current stream, no host sync."""
