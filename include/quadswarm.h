@@ -302,13 +302,14 @@ int qs_step_seq(qs_handle* h, int n, const float* const* actions,
  *    write is QS_E_INVALID.
  *  - Alignment.  Actions need 4-byte alignment only, and steps may share action
  *    buffers.  No output may overlap another output or any action buffer
- *    (QS_E_INVALID).  Nothing is cut into several launches: state cannot be
- *    carried between launches.
+ *    (QS_E_INVALID).  Nothing is cut into several launches: qs_score keeps no
+ *    branch state between launches (a branch set does: qs_branch_advance).
  *  - Depth.  1 <= n <= qs_score_depth(h): 32, lowered only where the steps'
  *    action rows (256 · A bytes per step and workgroup) plus the kernel's other
  *    LDS would pass the 64 KB a workgroup of the action-sequence launches may
  *    take.  It depends neither on C nor on QS_MAX_FUSED_STEPS.  Longer horizons
- *    are refused, not approximated.
+ *    are refused here, not approximated: chain qs_branch_advance calls on a
+ *    branch set (qs_branch_create) for them.
  *  - Handles that cannot score: qs_score_depth returns 0 and qs_score
  *    QS_E_INVALID with a message for handles that run the deferred reset search
  *    after each step (MultiHover layouts whose reset draws can be rejected) and
@@ -360,6 +361,89 @@ int qs_score(qs_handle* h, int n, int C, const float* const* actions,
 int qs_score_agents(qs_handle* h, int n, int C, const float* const* actions,
                     const qs_step_out* outs, const qs_score_out* score,
                     double* ret_agent, void* stream);
+
+/* Branch sets: branch rollouts that persist.  A branch set owns the state of
+ * C · E virtual envs (virtual env v = c · E + e, as in qs_score), so a rollout can
+ * go on from one launch to the next, be forked from the handle again, or be
+ * resampled: horizons past qs_score_depth, beam search, particle planners.  (New
+ * entry points of ABI 4, like qs_step_seq.)
+ *
+ * A branch set is bound to one handle, which must outlive it, and owns its device
+ * memory: the agent block [QS_AGENT_FIELDS][C · E · D] in the handle's precision,
+ * the four env fields of QS_STATE_ENV per virtual env, the action-history ring
+ * [H][C · E · D][A] and the three accumulators below (and as much again, which
+ * qs_branch_select gathers into).  It keeps no episode log, no reset-error flag
+ * and no episode returns: nothing in a branch reads them.  Every call but create /
+ * destroy / buffers / steps is stream-ordered and asynchronous, reads nothing
+ * back to the host and may be captured into a graph.  Like a handle, a branch set
+ * is used from one host thread at a time.
+ *
+ *  - qs_branch_fork.  Every candidate of env e becomes a copy of the handle's env
+ *    e (agent state, env counters, history ring) as the handle is at that point
+ *    of the stream: a snapshot, which later steps of the handle do not change.
+ *    ret and ret_agent become 0, first_done 0 and steps 0.  QS_E_STATE before
+ *    qs_reset.
+ *  - qs_branch_advance.  n steps, 1 <= n <= qs_score_depth(h), in one launch:
+ *    the qs_score launch with the state loaded from the set and stored back to
+ *    it.  actions[j]: [C][E][D][A] float32; outs: NULL, or n sets of step outputs
+ *    over C · E envs, laid out exactly as for qs_score (every pointer optional;
+ *    outs == NULL is valid here, since the state and the accumulators are
+ *    written).  For every candidate the per-step outputs of a chain of advances
+ *    equal, bit for bit, what qs_step_seq writes on a handle that started from
+ *    the forked state and ran the candidate's actions; the reset draws inside a
+ *    branch are keyed on the source env's global id (env_offset + e) and the
+ *    branch's own episode counter.  qs_score's alignment, overlap and 32-bit
+ *    size rules hold, and no named buffer may lie in the set's own memory.  Call
+ *    it any number of times: that is how the horizon grows.  QS_E_STATE before
+ *    the first fork.
+ *  - Accumulators.  With t = steps before the call, an env of a candidate is
+ *    live iff first_done == t.  While live, ret += (double)reward in step order
+ *    and each drone's ret_agent grows by its own term, exactly as in
+ *    qs_score_agents; first_done becomes the index since the fork of the first
+ *    done step, or t + n if there is still none.  After its first done step the
+ *    env keeps stepping (and resets, with auto-reset on, as in qs_score) and
+ *    its accumulators are frozen.  A chain of total length <= qs_score_depth
+ *    therefore writes the same bytes as one qs_score_agents call.
+ *  - qs_branch_select.  parent: device int32 [C][E].  The new candidate c of env
+ *    e takes the state and the three accumulators of the old candidate
+ *    parent[c][e] of the same env; a value outside 0 .. C-1 keeps candidate c.
+ *    All candidates read the old set, so duplicates and permutations are both
+ *    well defined.  steps is unchanged, and the pointers of qs_branch_buffers
+ *    stay valid and current (the gather goes into the set's second allocation
+ *    and is copied back on the device, on every replay of a captured call).
+ *    QS_E_STATE before the first fork.
+ *  - qs_branch_state.  Copies QS_STATE_AGENT ([fields][C · E · D]), QS_STATE_ENV
+ *    ([4][C · E] int32) or QS_STATE_HISTORY ([H][C · E · D][A]) into buf (device);
+ *    QS_STATE_EP_RETURN: QS_E_INVALID.
+ *  - qs_branch_steps.  Host only: the steps advanced since the last fork, as
+ *    counted when the calls were made.  A captured advance carries the step index
+ *    of its capture, so a graph should hold the fork that its advances follow.
+ *  - No mutation.  No call changes the handle: its four state blocks, episode
+ *    log (records and total), reset-error flag, qs_launch_counts and
+ *    qs_ring_counts are byte for byte as before, as qs_score guarantees.  Like
+ *    any call on the handle, a branch call ends a growing captured qs_step node.
+ *  - Refusals (QS_E_INVALID with a message, nothing launched, *out untouched on
+ *    create): a handle with qs_score_depth(h) == 0; C < 1; a block of C · E · D
+ *    agents past the 32-bit offsets; n out of range; a NULL among actions[]; an
+ *    output that overlaps another output or an action buffer.                  */
+typedef struct qs_branch_bufs { /* device pointers owned by the set, stable until
+                                   qs_branch_destroy                             */
+  double* ret;          /* [C][E]    rewards up to the first done step, in double */
+  int32_t* first_done;  /* [C][E]    that step's index since the fork, or steps   */
+  double* ret_agent;    /* [C][E][D] each drone's own terms, as qs_score_agents   */
+} qs_branch_bufs;
+
+typedef struct qs_branch qs_branch;
+
+int qs_branch_create(qs_handle* h, int C, qs_branch** out);
+int qs_branch_destroy(qs_branch* b);
+int qs_branch_buffers(const qs_branch* b, qs_branch_bufs* out);
+int qs_branch_steps(const qs_branch* b, int64_t* out);
+int qs_branch_fork(qs_branch* b, void* stream);
+int qs_branch_advance(qs_branch* b, int n, const float* const* actions,
+                      const qs_step_out* outs, void* stream);
+int qs_branch_select(qs_branch* b, const int32_t* parent, void* stream);
+int qs_branch_state(qs_branch* b, int block, void* buf, void* stream);
 
 /* MPPI planner tick on top of qs_score: sample C candidate sequences round a
  * nominal one, score them from the handle's current state, and fold them back

@@ -4,7 +4,8 @@
 // step_mh.hip / step_spiral.hip / step_marl.hip (single step), their
 // *_fused.hip twins (several control steps per launch), step_mh_seq.hip /
 // step_spiral_seq.hip (the same over caller-supplied actions), step_mh_score.hip /
-// step_spiral_score.hip (branch rollouts that leave the handle alone) and
+// step_spiral_score.hip (branch rollouts that leave the handle alone),
+// step_mh_branch.hip / step_spiral_branch.hip (the same on a branch set's state) and
 // step_mh_hot.hip (MultiHover's shape-specialised multi-step instances).
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -20,6 +21,7 @@
 #include "step_launch.h"
 #include "step_fuse.h"
 #include "step_score.h"
+#include "step_branch.h"
 #include "step_trunc.h"
 #include "planner_link.h"
 
@@ -37,12 +39,64 @@ static_assert(qs::kScoreMaxSteps == qs::kMaxFuse && qs::kScoreStepBytes == qs::k
                   qs::kScoreStepOuts == qs::kFuseOuts,
               "step_score.h disagrees with step_kernel.h / step_fuse.h on a launch's steps, action rows or outputs");
 
+static_assert(qs::kBranchEnvRec == qs::kEnvRec, "step_branch.h disagrees with step_kernel.h on an env record's words");
+
 namespace qs {
 // Calibration kernel: dword per lane, grid-stride (MI355X_MICROARCH §HBM).
 __global__ void calib_copy_kernel(float* __restrict__ dst, const float* __restrict__ src, long long n) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long stride = (long long)gridDim.x * blockDim.x;
   for (; i < n; i += stride) dst[i] = src[i];
+}
+
+// ------------------------------------------------------------ branch sets: fork and select
+// One kernel moves every block of a branch set (qs_branch_fork, qs_branch_select).
+// A block is `rows` rows of `cand` candidates of `row` units each, a unit 16 or 4
+// bytes: agent state [field][c][E · D], env records [1][c][E], history
+// [slot][c][E · D · A], and the accumulators likewise.  dst[r][c][l] = src[r][pc][l]:
+//   fork   (src_cand = 1): pc = 0, the handle's row tiled to the C candidates;
+//   select (src_cand = C): pc = parent[c][e] where that is a candidate, else c, e the
+//          env unit l lies in (`per_env` units to an env; a 16-byte unit is chosen
+//          only where it does not straddle two envs);
+//   src = NULL: zeros.
+// Lane i of a wave moves unit i of a row, so every load and store is a whole
+// coalesced line of the [field][agent] layout; src and dst never alias (select
+// gathers into the set's shadow allocation, which is then copied back whole, so no
+// candidate reads what another has already overwritten).  Units of a block stay
+// below 2^31 (step_branch.h), so the index arithmetic is 32-bit.
+struct BranchSeg {
+  const void* src;
+  void* dst;
+  unsigned row, rows, cand, src_cand, per_env, unit;
+};
+struct BranchMove {
+  BranchSeg seg[kBranchBlocks];
+  const int32_t* parent;   // [C][E] (select) or NULL
+  unsigned C, E;
+};
+template <class U> __device__ __forceinline__ void branch_move_seg(const BranchSeg& g, const int32_t* parent, unsigned C, unsigned E) {
+  const unsigned per_cand = g.row, total = g.rows * g.cand * per_cand;
+  const U* const src = static_cast<const U*>(g.src);
+  U* const dst = static_cast<U*>(g.dst);
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    U v{};
+    if (src) {
+      const unsigned rc = i / per_cand, l = i - rc * per_cand;
+      const unsigned r = rc / g.cand, c = rc - r * g.cand;
+      unsigned pc = 0;
+      if (g.src_cand != 1) {
+        const int32_t p = parent[c * E + l / g.per_env];
+        pc = (p >= 0 && (unsigned)p < C) ? (unsigned)p : c;
+      }
+      v = src[(size_t)(r * g.src_cand + pc) * per_cand + l];
+    }
+    dst[i] = v;
+  }
+}
+__global__ void __launch_bounds__(256) branch_move_kernel(BranchMove m) {
+  const BranchSeg& g = m.seg[blockIdx.y];
+  if (g.unit == 16) branch_move_seg<uint4>(g, m.parent, m.C, m.E);
+  else branch_move_seg<uint32_t>(g, m.parent, m.C, m.E);
 }
 
 // ------------------------------------------------------------ episode log query
@@ -316,7 +370,8 @@ static qs::HotShape hot_shape_of(const qs_handle* h, const qs::ParamsMany<T>& P,
 // no deferred reset queue: the callers see to that); FUSE = 2: the same over the
 // actions P.act[0 .. P.nsteps-1], whose rows take LDS of their own (the caller
 // has capped P.nsteps by seq_depth); FUSE = 3: the FUSE = 2 launch over P.E
-// virtual envs (qs_score, P.nsteps within score_depth).  select_only: no launch.
+// virtual envs (qs_score, P.nsteps within score_depth); FUSE = 4: that launch on a
+// branch set's own blocks (qs_branch_advance).  select_only: no launch.
 template <class T, int FUSE>
 static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t st, LaunchInfo* info, bool select_only,
                          int* kind = nullptr) {
@@ -350,7 +405,7 @@ static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t
       }
     }
   }
-  if constexpr (FUSE == 2 || FUSE == 3) {
+  if constexpr (FUSE == 2 || FUSE == 3 || FUSE == 4) {
     lds = seq_lds_base(h, lds) + (size_t)P.nsteps * qs::kSeqStepBytes * (size_t)h->dims.act_dim;
     if (lds + kLdsStatic > kLdsBytes) return fail(QS_E_INVALID, "launch: the steps' action rows do not fit in LDS");
   }
@@ -362,7 +417,7 @@ static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t
   else if (s.task == QS_TASK_SPIRAL)
     ok = qs::launch_task<T, QS_TASK_SPIRAL, FUSE>(s.act_type, grid, lds, st, P, s.ctrl_freq, s.pyb_freq, s.physics, &fn,
                                                   select_only);
-  else if constexpr (FUSE == 2 || FUSE == 3)
+  else if constexpr (FUSE == 2 || FUSE == 3 || FUSE == 4)
     return fail(QS_E_INVALID, "launch: no action-sequence instances of the Flock / Meetup / LeaderFollower family");
   else
     ok = qs::launch_task<T, qs::kTaskMarl, FUSE>(s.act_type, grid, lds, st, P, s.ctrl_freq, s.pyb_freq, s.physics, &fn,
@@ -777,6 +832,115 @@ template <class T> static int score_impl(const char* who_c, qs_handle* h, int n,
   return launch_kernel<T, 3>(h, P, st, nullptr, false);
 }
 
+// ---------------------------------------------------------------- branch sets
+// The state of C · E virtual envs in one allocation (step_branch.h's six blocks),
+// and a second one of the same size that qs_branch_select gathers into.
+struct qs_branch {
+  qs_handle* h = nullptr;
+  int C = 0;
+  qs::BranchSizes sz{};
+  char* set = nullptr;      // the blocks; qs_branch_buffers' pointers lie in it
+  char* shadow = nullptr;   // select's gather target, copied back whole
+  int64_t steps = 0;        // advanced since the last fork
+  bool forked = false;
+  void* block(int i) const { return set + sz.offset[i]; }
+};
+enum { BR_AGENT = 0, BR_ENV = 1, BR_HIST = 2, BR_RET = 3, BR_FD = 4, BR_RET_AGENT = 5 };
+
+// The six blocks as branch_move_kernel's segments: `src` / `dst` the allocations
+// the blocks lie in (src = nullptr: the handle's own three state blocks, tiled,
+// and zeros for the accumulators).
+static qs::BranchMove branch_segments(const qs_branch* b, const char* src, char* dst, const int32_t* parent) {
+  const qs_handle* h = b->h;
+  const qs_dims& d = h->dims;
+  const unsigned E = (unsigned)d.num_envs, D = (unsigned)d.num_drones, C = (unsigned)b->C;
+  // bytes of one env's share of a row, and rows, per block
+  const unsigned env_bytes[qs::kBranchBlocks] = {D * (unsigned)d.precision, (unsigned)qs::kEnvRec * 4u,
+                                                 D * (unsigned)d.act_dim * 4u, 8u, 4u, D * 8u};
+  const unsigned rows[qs::kBranchBlocks] = {QS_AGENT_FIELDS, 1u, (unsigned)d.hist_len, 1u, 1u, 1u};
+  const void* const from_handle[qs::kBranchBlocks] = {h->st, h->env, h->hist, nullptr, nullptr, nullptr};
+  qs::BranchMove m;
+  std::memset(&m, 0, sizeof(m));
+  m.parent = parent;
+  m.C = C;
+  m.E = E;
+  for (int i = 0; i < qs::kBranchBlocks; ++i) {
+    qs::BranchSeg& g = m.seg[i];
+    g.unit = env_bytes[i] % 16u == 0 ? 16u : 4u;   // (every block starts 256-byte aligned; rows are whole envs)
+    g.per_env = env_bytes[i] / g.unit;
+    g.row = E * g.per_env;
+    g.rows = rows[i];
+    g.cand = C;
+    g.src_cand = src ? C : 1u;
+    g.src = src ? static_cast<const void*>(src + b->sz.offset[i]) : from_handle[i];
+    g.dst = dst + b->sz.offset[i];
+  }
+  return m;
+}
+static int branch_move(const qs_branch* b, const qs::BranchMove& m, hipStream_t st) {
+  uint64_t most = 0;
+  for (int i = 0; i < qs::kBranchBlocks; ++i) most = std::max<uint64_t>(most, b->sz.bytes[i] / m.seg[i].unit);
+  const unsigned gx = (unsigned)std::min<uint64_t>(std::max<uint64_t>((most + 255) / 256, 1), 2048);
+  hipLaunchKernelGGL(qs::branch_move_kernel, dim3(gx, qs::kBranchBlocks), dim3(256), 0, st, m);
+  HIP_TRY(hipGetLastError());
+  return QS_OK;
+}
+
+template <class T> static int branch_advance_impl(qs_branch* b, int n, const float* const* actions, const qs_step_out* outs,
+                                                  hipStream_t st) {
+  const std::string who = "qs_branch_advance: ";
+  qs_handle* h = b->h;
+  const qs_dims& d = h->dims;
+  uint64_t bytes[qs::kScoreOuts], act_bytes = 0;
+  const qs::ScoreShape shape{b->C, d.num_envs, d.num_drones, d.obs_dim, d.act_dim, d.precision};
+  if (!qs::score_sizes(shape, bytes, &act_bytes) || !qs::score_fits(act_bytes))
+    return fail(QS_E_INVALID, who + "C * num_envs * num_drones is too large for one launch (32-bit offsets)");
+  qs::ScoreRanges ranges;
+  bool room = true;
+  const char* const names[qs::kFuseOuts] = {"obs", "reward", "terminated", "truncated", "terminal_obs", "reasons", "actions_out"};
+  for (int j = 0; j < n; ++j) {
+    room = ranges.add(actions[j], act_bytes, true) && room;
+    if (!outs) continue;
+    const qs::FuseOuts fo = to_outs(outs[j]);
+    for (int i = 0; i < qs::kFuseOuts; ++i) {
+      if (!fo.p[i]) continue;
+      if (!qs::score_fits(bytes[i]))
+        return fail(QS_E_INVALID, who + names[i] + " of C * num_envs envs is too large (32-bit offsets)");
+      room = ranges.add(fo.p[i], bytes[i], false) && room;
+    }
+  }
+  room = ranges.add(b->set, b->sz.total, false) && room;   // the set itself is written: nothing named may lie in it
+  if (!room || ranges.overlap())
+    return fail(QS_E_INVALID, who + "an output overlaps another output, an action buffer or the branch set");
+  qs::ParamsBranch<T> P;
+  std::memset(&P, 0, sizeof(P));
+  fill_params(h, P);
+  P.mode = qs::MODE_STEP;
+  P.E_src = d.num_envs;
+  P.E = (int)b->sz.V;
+  P.N = (int)b->sz.N;
+  P.st = (T*)b->block(BR_AGENT);
+  P.env = (int32_t*)b->block(BR_ENV);
+  P.hist = (float*)b->block(BR_HIST);
+  P.log = nullptr;               // a branch logs no episodes and raises no reset error
+  P.err = nullptr;
+  P.reset_queue = nullptr;       // (score_refusal: none)
+  P.reset_pre = nullptr;
+  P.store_state = 1;
+  P.nsteps = n;
+  for (int j = 0; j < n; ++j) {
+    if (outs) P.io[j] = to_io<T>(outs[j]);
+    P.act[j] = actions[j];
+  }
+  P.ret = (double*)b->block(BR_RET);
+  P.first_done = (int32_t*)b->block(BR_FD);
+  P.ret_agent = (double*)b->block(BR_RET_AGENT);
+  P.t0 = (int)b->steps;
+  const int rc = launch_kernel<T, 4>(h, P, st, nullptr, false);
+  if (rc == QS_OK) b->steps += n;
+  return rc;
+}
+
 // planner.hip's view of a handle (planner_link.h).
 namespace qs {
 void handle_info(const qs_handle* h, HandleInfo* out) {
@@ -1152,6 +1316,122 @@ int qs_state_io(qs_handle* h, int block, void* buf, int dir, void* stream) {
   if (dir) HIP_TRY(hipMemcpyAsync(src, buf, bytes, hipMemcpyDeviceToDevice, st));
   else HIP_TRY(hipMemcpyAsync(buf, src, bytes, hipMemcpyDeviceToDevice, st));
   if (dir) h->reset_done = true;
+  return QS_OK;
+}
+
+// ---- branch sets (include/quadswarm.h)
+int qs_branch_create(qs_handle* h, int C, qs_branch** out) {
+  const std::string who = "qs_branch_create: ";
+  if (!h || !out) return fail(QS_E_INVALID, who + "null argument");
+  if (const char* why = score_refusal(h)) return fail(QS_E_INVALID, who + "this handle cannot score: " + why);
+  if (score_depth(h) < 1) return fail(QS_E_INVALID, who + "this handle cannot score: no step's action rows fit in LDS");
+  if (C < 1) return fail(QS_E_INVALID, who + "C must be >= 1");
+  const qs_dims& d = h->dims;
+  qs::BranchSizes sz;
+  if (!qs::branch_sizes(qs::BranchShape{C, d.num_envs, d.num_drones, d.hist_len, d.act_dim, QS_AGENT_FIELDS, d.precision}, &sz))
+    return fail(QS_E_INVALID, who + "a state block of C * num_envs * num_drones agents is too large (32-bit offsets)");
+  HIP_TRY(hipSetDevice(h->device));
+  auto* b = new (std::nothrow) qs_branch();
+  if (!b) return fail(QS_E_NOMEM, who + "host allocation failed");
+  b->h = h;
+  b->C = C;
+  b->sz = sz;
+  if (hipMalloc((void**)&b->set, sz.total) != hipSuccess || hipMalloc((void**)&b->shadow, sz.total) != hipSuccess ||
+      hipMemset(b->set, 0, sz.total) != hipSuccess || hipMemset(b->shadow, 0, sz.total) != hipSuccess) {
+    (void)hipGetLastError();
+    qs_branch_destroy(b);
+    return fail(QS_E_NOMEM, who + "hipMalloc failed");
+  }
+  *out = b;
+  return QS_OK;
+}
+
+int qs_branch_destroy(qs_branch* b) {
+  if (!b) return QS_OK;
+  (void)hipSetDevice(b->h->device);   // teardown: best effort, nothing to report to
+  if (b->set) (void)hipFree(b->set);
+  if (b->shadow) (void)hipFree(b->shadow);
+  delete b;
+  return QS_OK;
+}
+
+int qs_branch_buffers(const qs_branch* b, qs_branch_bufs* out) {
+  if (!b || !out) return fail(QS_E_INVALID, "qs_branch_buffers: null argument");
+  out->ret = (double*)b->block(BR_RET);
+  out->first_done = (int32_t*)b->block(BR_FD);
+  out->ret_agent = (double*)b->block(BR_RET_AGENT);
+  return QS_OK;
+}
+
+int qs_branch_steps(const qs_branch* b, int64_t* out) {
+  if (!b || !out) return fail(QS_E_INVALID, "qs_branch_steps: null argument");
+  *out = b->steps;
+  return QS_OK;
+}
+
+int qs_branch_fork(qs_branch* b, void* stream) {
+  if (!b) return fail(QS_E_INVALID, "qs_branch_fork: null branch set");
+  if (!b->h->reset_done) return fail(QS_E_STATE, "qs_branch_fork: call qs_reset first");
+  b->h->fuse.forget();
+  const int rc = branch_move(b, branch_segments(b, nullptr, b->set, nullptr), (hipStream_t)stream);
+  if (rc != QS_OK) return rc;
+  b->steps = 0;
+  b->forked = true;
+  return QS_OK;
+}
+
+int qs_branch_advance(qs_branch* b, int n, const float* const* actions, const qs_step_out* outs, void* stream) {
+  const std::string who = "qs_branch_advance: ";
+  if (!b) return fail(QS_E_INVALID, who + "null branch set");
+  qs_handle* h = b->h;
+  const int depth = score_depth(h);
+  if (n < 1 || n > depth)
+    return fail(QS_E_INVALID, who + "n = " + std::to_string(n) + " is outside 1 .. qs_score_depth = " + std::to_string(depth) +
+                                  " (call it again to go on: the branch set keeps the state)");
+  if (!actions) return fail(QS_E_INVALID, who + "actions is null");
+  for (int j = 0; j < n; ++j)
+    if (!actions[j]) return fail(QS_E_INVALID, who + "actions[" + std::to_string(j) + "] is null");
+  if (!b->forked) return fail(QS_E_STATE, who + "call qs_branch_fork first");
+  if (!qs::branch_steps_fit(b->steps, n))
+    return fail(QS_E_INVALID, who + "first_done could not hold the step index: fork again");
+  h->fuse.forget();
+  hipStream_t st = (hipStream_t)stream;
+  if (h->dims.precision == 8) return branch_advance_impl<double>(b, n, actions, outs, st);
+  return branch_advance_impl<float>(b, n, actions, outs, st);
+}
+
+int qs_branch_select(qs_branch* b, const int32_t* parent, void* stream) {
+  if (!b || !parent) return fail(QS_E_INVALID, "qs_branch_select: null argument");
+  if (!b->forked) return fail(QS_E_STATE, "qs_branch_select: call qs_branch_fork first");
+  b->h->fuse.forget();
+  hipStream_t st = (hipStream_t)stream;
+  // every candidate reads the old set: gather into the shadow, then copy it back whole
+  // (the set's pointers stay what they were, on every replay of a captured call too)
+  const int rc = branch_move(b, branch_segments(b, b->set, b->shadow, parent), st);
+  if (rc != QS_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(b->set, b->shadow, b->sz.total, hipMemcpyDeviceToDevice, st));
+  return QS_OK;
+}
+
+int qs_branch_state(qs_branch* b, int block, void* buf, void* stream) {
+  if (!b || !buf) return fail(QS_E_INVALID, "qs_branch_state: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  b->h->fuse.forget();
+  int which;
+  switch (block) {
+    case QS_STATE_AGENT: which = BR_AGENT; break;
+    case QS_STATE_HISTORY: which = BR_HIST; break;
+    case QS_STATE_ENV: {   // the external layout [4][C · E] int32, from the records
+      HIP_TRY(hipSetDevice(b->h->device));
+      const int V = (int)b->sz.V;
+      env_io_kernel<<<(V + 255) / 256, 256, 0, st>>>((int32_t*)b->block(BR_ENV), buf, V, true, false, nullptr);
+      HIP_TRY(hipGetLastError());
+      return QS_OK;
+    }
+    default: return fail(QS_E_INVALID, "qs_branch_state: bad block (a branch set keeps no episode returns)");
+  }
+  HIP_TRY(hipSetDevice(b->h->device));
+  HIP_TRY(hipMemcpyAsync(buf, b->block(which), b->sz.bytes[which], hipMemcpyDeviceToDevice, st));
   return QS_OK;
 }
 

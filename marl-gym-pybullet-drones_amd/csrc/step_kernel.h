@@ -317,7 +317,7 @@ template <class T> struct ParamsSeq : ParamsMany<T> {
 // Once more a type of its own: Params, ParamsMany and ParamsSeq keep their size.
 template <class T> struct ParamsScore : ParamsSeq<T> {
   int E_src;
-  int store_state;       // always 0: nothing is stored to the handle (see the end of step_kernel for why it exists)
+  int store_state;       // qs_score: always 0, nothing is stored to the handle (see the end of step_kernel for why it exists); a branch set: 1
   double* ret;           // [E] or NULL: the candidate's return up to its first done
   int32_t* first_done;   // [E] or NULL: that step, nsteps if none
   double* ret_agent;     // [E][D] or NULL: each drone's own reward terms (before the division by D) up to that step
@@ -328,9 +328,20 @@ template <class T> struct ParamsScore : ParamsSeq<T> {
 template <class T> struct ParamsRing : ParamsMany<T> {
   int period;
 };
+// Arguments of the branch-set instances (step_kernel FUSE = 4, qs_branch_advance):
+// the FUSE = 3 launch whose virtual envs own their state.  st, env and hist are the
+// branch set's blocks, indexed by the virtual env (N = C · E_src · D agents, E
+// virtual envs) and written back after the loop (store_state = 1); ret, first_done
+// and ret_agent are the set's accumulators, loaded before the loop and stored
+// after it; t0 = the steps the set has advanced since its fork.  E_src still
+// keys the reset draws (global env id of v mod E_src).  A type of its own again:
+// ParamsScore keeps its size.
+template <class T> struct ParamsBranch : ParamsScore<T> {
+  int t0;
+};
 template <class T, int FUSE>
-using KernelParams = std::conditional_t<FUSE == 3, ParamsScore<T>,
-    std::conditional_t<FUSE == 2, ParamsSeq<T>, std::conditional_t<FUSE != 0, ParamsMany<T>, Params<T>>>>;
+using KernelParams = std::conditional_t<FUSE == 4, ParamsBranch<T>, std::conditional_t<FUSE == 3, ParamsScore<T>,
+    std::conditional_t<FUSE == 2, ParamsSeq<T>, std::conditional_t<FUSE != 0, ParamsMany<T>, Params<T>>>>>;
 
 // ---------------------------------------------------- conversions (external)
 // pybullet getMatrixFromQuaternion = btMatrix3x3::setRotation (s = 2/|q|²).
@@ -859,6 +870,14 @@ template <class T> __device__ __forceinline__ int launch_src_envs(const ParamsSc
 // env's first lane also sums the rewards up to the first done step.  Each of
 // its statements is chosen by a compile-time test, so the other instances
 // compile to the code they had.
+// FUSE = 4: the FUSE = 3 loop over a branch set (qs_branch_advance, ParamsBranch):
+// the virtual envs' state, env records and history rings live in the set's own
+// blocks, so a rollout goes on from launch to launch.  Against FUSE = 3 it loads
+// by the virtual env, switches the after-loop state stores on, stores the history
+// ring once after the loop (from hreg[] as the ring instance does; from the LDS
+// image with a run-time control frequency) and the env records as the FUSE = 2
+// instances do, and loads and stores the three accumulators.  Still no episode
+// log, no error flag and no store to the handle.
 // HOT = 1 (FUSE = 1, MultiHover, compile-time control frequency, AUXM 0 only):
 // the launch shape qs::hot_shape_ok (step_fuse.h) accepts, with everything that
 // predicate fixes for the launch folded in ("hot shape"): D = 8
@@ -950,9 +969,15 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
   // history slot, the episode log, the error flag and the env record are compiled
   // out below, the final state stores skipped (ParamsScore::store_state, always
   // 0).  Actions and outputs index by e and a as ever.
-  constexpr bool kScore = FUSE == 3;
-  const int e_h = kScore ? e % launch_src_envs(P) : e, a_h = kScore ? e_h * D + d : a;
-  const uint32_t genv = (uint32_t)(P.env_offset + e_h);
+  // FUSE = 4 (qs_branch_advance): the same virtual envs, but each owns its state
+  // in the branch set's blocks, which P.st / P.env / P.hist name: it loads by e and
+  // a, stores the state, the history ring and the env record back after the loop,
+  // and carries the score from launch to launch (ParamsBranch).  Only the reset
+  // draws still go by the source env, v mod E_src.
+  constexpr bool kBranch = FUSE == 4;
+  constexpr bool kScore = FUSE == 3 || kBranch;
+  const int e_h = (kScore && !kBranch) ? e % launch_src_envs(P) : e, a_h = (kScore && !kBranch) ? e_h * D + d : a;
+  const uint32_t genv = (uint32_t)(P.env_offset + (kBranch ? e % launch_src_envs(P) : e_h));
   // kBlock == 64 is one wave: an env of 2, 4, 8 or 16 drones lies inside one
   // 16-lane DPP row, and the per-env reduction and flags need no LDS.  Multi-step
   // instances only: with the run-time choice between the two paths in it, the
@@ -978,7 +1003,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, (int)bytes, 0x00020000);
   };
   SA.voff = valid ? SA.voff : kOOB;
-  const unsigned E = (unsigned)launch_src_envs(P);   // the handle's envs
+  const unsigned E = kBranch ? (unsigned)P.E : (unsigned)launch_src_envs(P);   // the handle's envs (FUSE = 4: the set's)
   // env counters first: the synthetic action draw needs only `total`
   typedef unsigned v2u_t __attribute__((ext_vector_type(2)));
   static_assert(QS_E_STEP_COUNTER == 0 && QS_E_EPISODE == 1 && QS_E_TOTAL_STEPS == 2 && QS_E_EP_LEN == 3, "record");
@@ -996,6 +1021,15 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
   // null buffer reads 0 (num_records 0)
   const int32_t pre0 = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(
       rsrc(P.reset_pre, P.reset_pre ? E * 4u : 0u), valid ? (int)(e_h * 4u) : (int)kOOB, 0, 0);
+  // FUSE = 4: the set's accumulators (every lane of an env reads the env's two)
+  [[maybe_unused]] double acc_ret0 = 0, acc_agent0 = 0;
+  [[maybe_unused]] int32_t acc_fd0 = 0;
+  if constexpr (kBranch) {
+    acc_ret0 = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rsrc(P.ret, E * 8u), valid ? (int)(e * 8u) : (int)kOOB, 0, 0));
+    acc_fd0 = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc(P.first_done, E * 4u), valid ? (int)(e * 4u) : (int)kOOB, 0, 0);
+    acc_agent0 = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rsrc(P.ret_agent, (unsigned)N * 8u),
+                                                                               valid ? (int)((unsigned)a * 8u) : (int)kOOB, 0, 0));
+  }
   issue_fence();
   T pos[3], q[4], vel[3], w[3], lrpm[4], pid[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tgt[3] = {0, 0, 0};
 #pragma unroll
@@ -1046,7 +1080,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
   extern __shared__ float4 dyn_lds4[];   // float4: 16-B aligned staging for the obs stores
   // FUSE = 2: the launch's action rows come first, nsteps · A · kBlock floats
   // (a multiple of 256 bytes: the stage keeps its alignment)
-  constexpr bool kSeq = FUSE == 2 || FUSE == 3;
+  constexpr bool kSeq = FUSE == 2 || FUSE == 3 || FUSE == 4;
   float* const dyn_lds = reinterpret_cast<float*>(dyn_lds4);
   float* const act_lds = dyn_lds;
   float* const hist_pref = kSeq ? dyn_lds + (size_t)launch_steps(P) * kBlock * A : dyn_lds;
@@ -1067,7 +1101,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
         hreg[sl][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(hr, (int)(hv + 4u * k), so, 0));
     }
   } else {
-    const int a_src = valid ? a_h : (kScore ? (int)((blockIdx.x * P.EPB) % launch_src_envs(P)) * D : blockIdx.x * P.EPB * D);   // idle lanes read a valid row
+    const int a_src = valid ? a_h : ((kScore && !kBranch) ? (int)((blockIdx.x * P.EPB) % launch_src_envs(P)) * D : blockIdx.x * P.EPB * D);   // idle lanes read a valid row
     for (int sl = 0; sl < H; ++sl) {
       const float* src = P.hist + ((size_t)sl * N + a_src) * A;
       if constexpr (A == 1) {
@@ -1128,6 +1162,15 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
   // while its env has not ended
   [[maybe_unused]] double score_agent = 0;
   [[maybe_unused]] bool score_live = true;
+  // FUSE = 4: they go on from the set's; an env is live iff it was never done since the fork
+  [[maybe_unused]] int score_t0 = 0;
+  if constexpr (kBranch) {
+    score_t0 = P.t0;
+    score_ret = acc_ret0;
+    score_agent = acc_agent0;
+    score_live = acc_fd0 == score_t0;
+    score_fd = score_live ? -1 : acc_fd0;
+  }
 
   float cur_act[A];            // this step's action (newest history entry)
 #pragma unroll
@@ -1812,7 +1855,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
       if constexpr (kScore) {   // the candidate's return, up to and including its first done step
         if (score_fd < 0) {
           score_ret += (double)r;
-          if (dn) score_fd = ks;
+          if (dn) score_fd = kBranch ? score_t0 + ks : ks;
         }
       }
     }
@@ -2126,7 +2169,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
     if constexpr (kAged) {   // every entry ages by one step; this step's action is the newest older entry
       // ring: the entry that ages out is what the next write slot holds; hreg[HR − 1]
       // (the first write slot's content since the rotation) carries it to the stores after the loop
-      if constexpr (kRingHist) {
+      if constexpr (kRingHist || kBranch) {   // (FUSE = 4 stores the ring after the loop in the same way)
 #pragma unroll
         for (int k = 0; k < A; ++k) hreg[HR - 1][k] = hreg[0][k];
       }
@@ -2170,15 +2213,36 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
       store_act<A>(QS_LAUNCH_VAL(hist) + ((size_t)sl * N + a) * A, hreg[j]);
     }
   }
+  // FUSE = 4: the branch set's ring, once, from hreg[] as the ring instance's; with a
+  // run-time control frequency from the LDS image, which the steps kept current
+  if constexpr (kBranch) {
+    if (valid) {
+      if constexpr (CF != 0) {
+#pragma unroll
+        for (int j = 0; j < HR; ++j) {
+          int sl = wslot + 1 + j;
+          sl -= sl >= HR ? HR : 0;
+          store_act<A>(P.hist + ((size_t)sl * N + a) * A, hreg[j]);
+        }
+      } else {
+        for (int sl = 0; sl < H; ++sl) {
+          float hv[A];
+#pragma unroll
+          for (int k = 0; k < A; ++k) hv[k] = hist_at(sl, k);
+          store_act<A>(P.hist + ((size_t)sl * N + a) * A, hv);
+        }
+      }
+    }
+  }
   if constexpr (kScore) {   // the candidate's score, by the env's first lane
     if (valid && d == 0) {
       if (P.ret) P.ret[e] = score_ret;
-      if (P.first_done) P.first_done[e] = score_fd < 0 ? launch_steps(P) : score_fd;
+      if (P.first_done) P.first_done[e] = score_fd < 0 ? (kBranch ? score_t0 : 0) + launch_steps(P) : score_fd;
     }
     if (valid && P.ret_agent) P.ret_agent[a] = score_agent;   // a < C · E · D < 2^31 (step_score.h)
   }
   // ---------------- per-env records: staged in LDS, stored as one span
-  if constexpr (!kScore) {
+  if constexpr (!kScore || kBranch) {
   if (valid && d == 0) {
     int32_t* r = &s.rec[lenv * kEnvRec];
     const unsigned long long rb = __builtin_bit_cast(unsigned long long, ep_ret_out);

@@ -3,9 +3,10 @@
 //
 // qs_score runs C candidate action sequences of n steps from the handle's state
 // in one launch of the FUSE = 3 step kernel over C · E virtual envs and stores
-// nothing to the handle.  State cannot be carried from one launch to the next,
+// nothing to the handle.  qs_score keeps no state from one launch to the next,
 // so nothing is cut into several launches: a call is refused where a launch
-// could not hold it.  Three decisions are plain arithmetic and live here: how
+// could not hold it (a branch set carries the state between launches:
+// qs_branch_advance, step_branch.h).  Three decisions are plain arithmetic and live here: how
 // many steps a launch takes (the steps' action rows wait in LDS), how many
 // bytes each output of the C · E virtual envs covers, and whether the buffers
 // the caller named keep out of each other's way.

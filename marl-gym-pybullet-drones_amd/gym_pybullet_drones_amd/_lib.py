@@ -60,6 +60,11 @@ class QsScoreOut(ctypes.Structure):
     _fields_ = [("ret", ctypes.c_void_p), ("first_done", ctypes.c_void_p)]
 
 
+class QsBranchBufs(ctypes.Structure):
+    """include/quadswarm.h qs_branch_bufs: a branch set's accumulators (device pointers)."""
+    _fields_ = [("ret", ctypes.c_void_p), ("first_done", ctypes.c_void_p), ("ret_agent", ctypes.c_void_p)]
+
+
 class QsMppiSpec(ctypes.Structure):
     """include/quadswarm.h qs_mppi_spec: what a planner is created from."""
     _fields_ = [("horizon", ctypes.c_int32), ("candidates", ctypes.c_int32), ("sigma", ctypes.c_float * 4),
@@ -98,7 +103,9 @@ EXPORTS = ("qs_create", "qs_destroy", "qs_last_error", "qs_abi_version", "qs_get
            "qs_mppi_create", "qs_mppi_destroy", "qs_mppi_buffers", "qs_mppi_reset", "qs_mppi_sample", "qs_mppi_update",
            "qs_mppi_plan", "qs_cem_create", "qs_cem_destroy", "qs_cem_buffers", "qs_cem_reset", "qs_cem_begin", "qs_cem_sample",
            "qs_cem_refit", "qs_cem_finish", "qs_cem_plan", "qs_score_agents", "qs_pd_mppi_create", "qs_pd_mppi_ret_agent",
-           "qs_pd_cem_create", "qs_pd_cem_ret_agent", "qs_launch_counts", "qs_ring_counts", "qs_state_io", "qs_episode_log", "qs_reset_error", "qs_calib_copy",
+           "qs_pd_cem_create", "qs_pd_cem_ret_agent",
+           "qs_branch_create", "qs_branch_destroy", "qs_branch_buffers", "qs_branch_steps", "qs_branch_fork",
+           "qs_branch_advance", "qs_branch_select", "qs_branch_state", "qs_launch_counts", "qs_ring_counts", "qs_state_io", "qs_episode_log", "qs_reset_error", "qs_calib_copy",
            # include/qs_learner.h
            "qs_gae", "qs_adam_gated", "qs_adam_commit", "qs_ppo_heads", "qs_ppo_heads_work_bytes",
            "qs_mlp_bias_tanh", "qs_mlp_bwd_blocks", "qs_mlp_tanh_bwd", "qs_mlp_sum_partials",
@@ -188,6 +195,15 @@ def load():
         L.qs_pd_mppi_ret_agent.argtypes = [vp, ctypes.POINTER(vp)]
         L.qs_pd_cem_create.argtypes = [vp, ctypes.POINTER(QsCemSpec), ctypes.POINTER(vp)]
         L.qs_pd_cem_ret_agent.argtypes = [vp, ctypes.POINTER(vp)]
+    if hasattr(L, "qs_branch_create"):   # (a QS_DEV_LIB build from before the entry points: A/B runs)
+        L.qs_branch_create.argtypes = [vp, i32, ctypes.POINTER(vp)]
+        L.qs_branch_destroy.argtypes = [vp]
+        L.qs_branch_buffers.argtypes = [vp, ctypes.POINTER(QsBranchBufs)]
+        L.qs_branch_steps.argtypes = [vp, ctypes.POINTER(i64)]
+        L.qs_branch_fork.argtypes = [vp, vp]
+        L.qs_branch_advance.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(QsStepOut), vp]
+        L.qs_branch_select.argtypes = [vp, vp, vp]
+        L.qs_branch_state.argtypes = [vp, i32, vp, vp]
     if hasattr(L, "qs_launch_counts"):   # (a QS_DEV_LIB build from before the entry point: A/B runs)
         L.qs_launch_counts.argtypes = [vp, ctypes.POINTER(i64)]
     if hasattr(L, "qs_ring_counts"):
@@ -258,7 +274,7 @@ def load():
     L.qs_rms_update.argtypes = [i64, ctypes.c_int32] + [vp] * 7
     L.qs_rms_normalize.argtypes = [i64, ctypes.c_int32, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp]
     for name in EXPORTS:
-        if (name in ("qs_launch_counts", "qs_ring_counts", "qs_score_depth", "qs_score") or name.startswith(("qs_mppi_", "qs_cem_", "qs_pd_"))
+        if (name in ("qs_launch_counts", "qs_ring_counts", "qs_score_depth", "qs_score") or name.startswith(("qs_mppi_", "qs_cem_", "qs_pd_", "qs_branch_"))
                 or name == "qs_score_agents") and not hasattr(L, name):
             continue   # (a QS_DEV_LIB build from before the entry point)
         if name not in ("qs_last_error", "qs_learner_last_error", "qs_rms_last_error", "qs_ppo_small_last_error",

@@ -345,6 +345,16 @@ class QuadSwarm:
         L.check(self.lib.qs_score_agents(self._h, n, C, ptrs, arr, so, buf(ret_agent, "ret_agent"), self._stream()),
                 "qs_score_agents")
 
+    def branches(self, C):
+        """A `BranchSet` of C candidates on this swarm (qs_branch_create): the state
+        of C · E virtual envs kept on the device, so that branch rollouts can be
+        chained past score_depth(), forked from the swarm again and resampled."""
+        if not hasattr(self.lib, "qs_branch_create"):
+            raise L.QuadSwarmError(f"{L.LIB_PATH} has no qs_branch_create: rebuild the HIP extension")
+        bs = BranchSet(self, C)
+        self.__dict__.setdefault("_planners", weakref.WeakSet()).add(bs)   # close() ends them first
+        return bs
+
     def mppi(self, horizon, candidates, sigma, lo=-1.0, hi=1.0, lam=1.0, done_penalty=0.0, seed=0, per_drone=False):
         """An `MPPIPlanner` on this swarm (qs_mppi_create): `candidates` action
         sequences of `horizon` steps (1 .. score_depth()) are drawn round a nominal
@@ -439,6 +449,155 @@ class _DeviceSpan:
     def __init__(self, ptr, shape, typestr):
         self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False),
                                          "version": 2, "strides": None}
+
+
+class BranchSet:
+    """Persistent branch rollouts on a swarm (qs_branch_*, include/quadswarm.h).
+
+    The set owns the state of C · E virtual envs (candidate c of env e).  `fork()`
+    makes every candidate of env e a copy of the swarm's env e as it is at that
+    point of the stream; `advance(actions, outs)` runs 1 .. score_depth() steps of
+    every candidate in one launch, from the set's state and back into it;
+    `rollout(actions, outs)` takes any number of steps and chains `advance` in
+    chunks of at most score_depth(); `select(parent)` makes candidate c of env e a
+    copy of the old candidate parent[c, e] of that env (a value outside 0 .. C-1
+    keeps it).  The swarm itself is never changed.  Every call is stream-ordered
+    with no host sync and may be captured into a graph (with the fork its advances
+    follow: a captured advance carries the step index of its capture).
+
+    `ret` (C, E) float64, `first_done` (C, E) int32 and `ret_agent` (C, E, D)
+    float64 are torch tensors over the set's own device memory (no copies; they
+    dangle after `close()`), accumulated since the last fork as `QuadSwarm.score`
+    forms them: an env's rewards count up to its first done step, whose index
+    since the fork `first_done` holds (`steps` while there is none).  `steps`: the
+    steps advanced since the last fork.  The swarm must outlive the set."""
+
+    def __init__(self, swarm, C):
+        self.swarm, self.lib, self.num_candidates = swarm, swarm.lib, int(C)
+        self._p = ctypes.c_void_p()
+        with torch.cuda.device(swarm.device):
+            L.check(self.lib.qs_branch_create(swarm._h, self.num_candidates, ctypes.byref(self._p)), "qs_branch_create")
+        bufs = L.QsBranchBufs()
+        L.check(self.lib.qs_branch_buffers(self._p, ctypes.byref(bufs)), "qs_branch_buffers")
+        C, E, D = self.num_candidates, swarm.num_envs, swarm.num_drones
+        for name, shape, typestr in (("ret", (C, E), "<f8"), ("first_done", (C, E), "<i4"), ("ret_agent", (C, E, D), "<f8")):
+            setattr(self, name, torch.as_tensor(_DeviceSpan(getattr(bufs, name), shape, typestr), device=swarm.device))
+
+    def _stream(self):
+        return self.swarm._stream()
+
+    @property
+    def steps(self):
+        v = ctypes.c_int64(0)
+        L.check(self.lib.qs_branch_steps(self._p, ctypes.byref(v)), "qs_branch_steps")
+        return int(v.value)
+
+    def fork(self):
+        L.check(self.lib.qs_branch_fork(self._p, self._stream()), "qs_branch_fork")
+
+    def _steps_of(self, actions):
+        sw, C = self.swarm, self.num_candidates
+        shape = (C, sw.num_envs, sw.num_drones, sw.act_dim)
+        if isinstance(actions, torch.Tensor):
+            if actions.dim() != 5:
+                raise ValueError(f"actions must be (n,) + {shape} or a list of {shape} tensors")
+            acts = [actions[j] for j in range(actions.shape[0])]
+        else:
+            acts = list(actions)
+        if len(acts) < 1:
+            raise ValueError(f"actions must hold at least one step of shape {shape}")
+        for a in acts:
+            if (not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or not a.is_contiguous()
+                    or a.device != sw.device or tuple(a.shape) != shape):
+                raise ValueError(f"actions: every step must be a contiguous float32 {shape} tensor on {sw.device}")
+        return acts
+
+    def _outs_of(self, outs, n):
+        if outs is None:
+            return None
+        sw, C = self.swarm, self.num_candidates
+        E, D, A, O = sw.num_envs, sw.num_drones, sw.act_dim, sw.obs_dim
+        want = dict(obs=(torch.float32, C * E * D * O), reward=(sw.rdtype, C * E), terminated=(torch.uint8, C * E),
+                    truncated=(torch.uint8, C * E), terminal_obs=(torch.float32, C * E * D * O),
+                    reasons=(torch.uint8, C * E * D), actions_out=(torch.float32, C * E * D * A))
+        if len(outs) != n:
+            raise ValueError(f"outs must hold {n} steps, one dict each")
+        recs = []
+        for kw in outs:
+            unknown = set(kw) - set(want)
+            if unknown:
+                raise ValueError(f"outs: unknown output {sorted(unknown)}")
+            ptrs = []
+            for k in QuadSwarm._SCORE_OUTS:
+                t = kw.get(k)
+                if t is not None:
+                    dt, numel = want[k]
+                    if (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous() or t.numel() < numel
+                            or t.device != sw.device):
+                        raise ValueError(f"{k} must be a contiguous {dt} tensor of >= {numel} elements on {sw.device}")
+                ptrs.append(L.ptr(t))
+            recs.append(L.QsStepOut(*ptrs))
+        return recs
+
+    def _advance(self, acts, recs):
+        n = len(acts)
+        ptrs = (ctypes.c_void_p * n)(*[a.data_ptr() for a in acts])
+        arr = None if recs is None else (L.QsStepOut * n)(*recs)
+        L.check(self.lib.qs_branch_advance(self._p, n, ptrs, arr, self._stream()), "qs_branch_advance")
+
+    def advance(self, actions, outs=None):
+        """n = len(actions) steps, 1 <= n <= score_depth(), in one launch.  actions: one
+        (n, C, E, D, A) float32 tensor, whose slices are passed as they are (no copy),
+        or a list of n (C, E, D, A) tensors; outs: None, or one dict of step()'s
+        output keywords per step, each buffer stacked over the candidates as in
+        `QuadSwarm.score`."""
+        acts = self._steps_of(actions)
+        self._advance(acts, self._outs_of(outs, len(acts)))
+
+    def rollout(self, actions, outs=None):
+        """`advance` for any n >= 1: the steps are cut into launches of at most
+        score_depth() steps, in order."""
+        acts = self._steps_of(actions)
+        recs = self._outs_of(outs, len(acts))
+        depth = self.swarm.score_depth()
+        for j in range(0, len(acts), depth):
+            self._advance(acts[j:j + depth], None if recs is None else recs[j:j + depth])
+
+    def select(self, parent):
+        """parent: (C, E) int32 on the device."""
+        sw = self.swarm
+        if (not isinstance(parent, torch.Tensor) or parent.dtype != torch.int32 or not parent.is_contiguous()
+                or parent.device != sw.device or tuple(parent.shape) != (self.num_candidates, sw.num_envs)):
+            raise ValueError(f"parent must be a contiguous int32 ({self.num_candidates},{sw.num_envs}) tensor on {sw.device}")
+        L.check(self.lib.qs_branch_select(self._p, L.ptr(parent), self._stream()), "qs_branch_select")
+
+    def get_state(self, block=L.STATE_AGENT) -> torch.Tensor:
+        """The set's copy of a state block, stacked over the candidates: STATE_AGENT
+        (fields, C, E · D), STATE_ENV (4, C, E) or STATE_HISTORY (H, C, E · D, A)."""
+        sw, C = self.swarm, self.num_candidates
+        kw = dict(device=sw.device)
+        if block == L.STATE_AGENT:
+            buf = torch.zeros((L.AGENT_FIELDS, C, sw.num_agents), dtype=sw.rdtype, **kw)
+        elif block == L.STATE_ENV:
+            buf = torch.zeros((L.ENV_FIELDS, C, sw.num_envs), dtype=torch.int32, **kw)
+        elif block == L.STATE_HISTORY:
+            buf = torch.zeros((sw.hist_len, C, sw.num_agents, sw.act_dim), dtype=torch.float32, **kw)
+        else:
+            raise ValueError(block)
+        L.check(self.lib.qs_branch_state(self._p, block, L.ptr(buf), self._stream()), "qs_branch_state")
+        return buf
+
+    def close(self):
+        if getattr(self, "_p", None):
+            torch.cuda.synchronize(self.swarm.device)
+            self.lib.qs_branch_destroy(self._p)
+            self._p = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class _Planner:

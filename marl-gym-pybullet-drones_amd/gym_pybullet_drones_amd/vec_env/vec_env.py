@@ -235,6 +235,12 @@ class SwarmVecEnv(VecEnv):
             res += (own["ret_agent"],)
         return res
 
+    def branches(self, C):
+        """A `BranchSet` of C candidates on these envs (QuadSwarm.branches): branch
+        rollouts that keep their state, so they can be chained past score_depth(),
+        forked again and resampled."""
+        return self.swarm.branches(C)
+
     def mppi(self, horizon, candidates, sigma, **kw):
         """An `MPPIPlanner` on these envs (QuadSwarm.mppi, same arguments, `per_drone`
         among them).  Its
