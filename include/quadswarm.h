@@ -653,6 +653,138 @@ int qs_pd_mppi_ret_agent(const qs_mppi* p, double** out);
 int qs_pd_cem_create(qs_handle* h, const qs_cem_spec* spec, qs_cem** out);
 int qs_pd_cem_ret_agent(const qs_cem* p, double** out);
 
+/* Particle (sequential Monte Carlo) planner tick on top of a branch set: fork C
+ * particles from the handle's current state, run the horizon in S = ceil(n / L)
+ * segments of at most L steps, each "sample actions, advance the particles, weigh
+ * them and systematically resample per env", trace every surviving particle's
+ * action sequence back through the resampling steps and fold the sequences into
+ * the nominal by their weights, as MPPI does, all on the device.  The horizon is
+ * not held to qs_score_depth: only a segment is.  With ess_frac = 0 nothing is
+ * ever resampled and the tick is an MPPI tick of any length.  (New entry points of
+ * ABI 4, like qs_branch_*.)
+ *
+ * A planner is bound to one handle, which must outlive it, and owns its device
+ * buffers (qs_smc_buffers; stable until qs_smc_destroy) and one branch set of C
+ * candidates (qs_branch_create), which qs_smc_branch hands out for reading only
+ * (qs_branch_buffers, qs_branch_state, qs_branch_steps): the caller neither
+ * destroys nor forks it.  ret, first_done and ret_agent are that set's.  Every call
+ * but create / destroy / buffers / branch is stream-ordered and asynchronous,
+ * reads nothing back to the host and may be captured into a graph; the tick
+ * counter lives on the device, so a replayed graph draws new noise each time.  No
+ * float atomics and every sum in a fixed order: the same inputs give the same
+ * bytes.  Like a handle, a planner is used from one host thread at a time.  Every
+ * env plans independently of the others.
+ *
+ * Segment s holds the steps s · L .. min(n, (s + 1) · L) - 1 of the tick.
+ *
+ *  - qs_smc_begin.  qs_branch_fork of the set; base = 0; parents[s][c][e] = c for
+ *    every s; resampled, offset and ess = 0.  QS_E_STATE before qs_reset, with
+ *    nothing launched.
+ *  - qs_smc_sample(p, s).  qs_mppi_sample's kernel over the steps of segment s: one
+ *    Philox4x32-10 call per (step j, particle c, env e, drone d): key = seed,
+ *    counter = (low word of *tick, env_offset + e, c · 32 + (j - s · L),
+ *    (5 << 24) | (s << 8) | d), the normals formed as in qs_mppi_sample.
+ *    candidates[j][0][e][d][a] = nominal[j][e][d][a] as it is (particle 0 draws no
+ *    noise); for c > 0, clamp(nominal + sigma[a] · z_a, lo, hi), the sum left out
+ *    where sigma[a] = 0.  The counter holds the global env id, so the noise does
+ *    not depend on how envs are sharded; segments, ticks, envs, particles, steps
+ *    and drones never share a counter.
+ *  - qs_smc_advance(p, s).  qs_branch_advance of the segment's steps from
+ *    candidates, with outs = NULL.  QS_E_STATE before the first begin.
+ *  - qs_smc_resample(p, s), 0 <= s < S - 1.  Per env e, in double, with t =
+ *    (s + 1) · L the steps since the fork: score_c = ret[c][e] - (first_done[c][e]
+ *    < t ? done_penalty : 0); logw_c = (score_c - base[c][e]) / lambda; x_c =
+ *    exp(logw_c - max logw) and weights[c][e] = x_c / sum over c.  A NaN logw
+ *    gives weight 0 (and is passed over by the max); where no logw is a number
+ *    the weights are uniform and the env does not resample.  ess[s][e] = 1 / sum
+ *    over c of weights^2.  The env resamples iff ess < ess_frac · C, which
+ *    resampled[s][e] records.  If it does: one Philox call per env, key = seed,
+ *    counter = (low word of *tick, env_offset + e, s, 6 << 24), u = (x0 >> 8) ·
+ *    2^-24 in [0, 1) into offset[s][e]; with pos_i = (i + u) / C,
+ *    parents[s][i][e] = the lowest c whose inclusive cumulative weight (in index
+ *    order) exceeds pos_i, C - 1 if none does; base[i][e] = score of that
+ *    parent, so every new particle starts the next segment at log weight 0.  If
+ *    it does not: parents[s][.][e] is the identity, base is untouched and
+ *    offset[s][e] = 0.  Then qs_branch_select(set, parents[s]).  The cumulative
+ *    sum's rounding is the variant's own: one thread per env adds the weights up
+ *    in index order; the workgroup per env (C >= 64 and few envs, the criterion
+ *    of the MPPI update's variants) scans them in blocks and takes the running
+ *    maximum of the scan, so that it never falls; either is within C · 2^-53 of
+ *    the exact sum.  It reads ret and first_done as they are: a caller may
+ *    overwrite them through the set's pointers first.  With ess_frac = 0, and for
+ *    s = S - 1 (finish weighs the last segment), nothing is launched and the call
+ *    returns QS_OK.  QS_E_STATE before the first begin.
+ *  - qs_smc_finish.  weights from the final logw as above, with t = n, and
+ *    ess[S - 1][e] from them; best[e] = the lowest c with the largest weight;
+ *    ancestors[S - 1][c][e] = c and ancestors[s][c][e] = parents[s][ancestors[s +
+ *    1][c][e]][e] for s = S - 2 .. 0; new[j] = (float) sum over c of
+ *    weights[c][e] · candidates[j][ancestors[s(j)][c][e]][e], s(j) = j / L, summed
+ *    in double; action = new[0]; nominal[j] = new[j + 1] for j < n - 1 and
+ *    nominal[n - 1] = new[n - 1] (hold); *tick += 1.  Three launches.
+ *  - qs_smc_plan = begin, then for s = 0 .. S - 1: sample(s), advance(s),
+ *    resample(s), then finish.  QS_E_STATE before qs_reset, with nothing launched.
+ *  - qs_smc_reset copies `nominal` (device, [n][E][D][A]; NULL: zeros) into the
+ *    planner and sets *tick = 0.  A new planner is in that state with zeros.
+ *  - Per-drone mode: none.  A branch's state is shared by the env's drones, so the
+ *    drones of an env cannot be resampled apart.
+ *  - qs_smc_create refusals (QS_E_INVALID with a message, nothing launched, *out
+ *    untouched): horizon < 1 or more than 256 segments, segment outside 1 ..
+ *    qs_score_depth(h), particles < 2 or > 4096 (the workgroup variant keeps one
+ *    env's cumulative weights in LDS, four particles to each of its 1024
+ *    threads), lo >= hi or non-finite, a negative or non-finite sigma or
+ *    done_penalty, lambda <= 0 or non-finite, ess_frac outside [0, 1], whatever
+ *    qs_branch_create refuses (a handle with qs_score_depth(h) = 0 among it), and
+ *    sizes beyond the 32-bit offsets of a branch advance or S · C · E >= 2^31.
+ *    qs_smc_sample / advance / resample with s outside 0 .. S - 1: QS_E_INVALID,
+ *    nothing launched.                                                          */
+typedef struct qs_smc_spec {
+  int32_t horizon;      /* n >= 1 steps per tick; S = ceil(n / segment) <= 256     */
+  int32_t segment;      /* L: 1 .. qs_score_depth(h) steps per advance; the last
+                           segment may be shorter                                 */
+  int32_t particles;    /* C: 2 .. 4096; particle 0 draws no noise (it follows the
+                           nominal's actions)                                     */
+  float sigma[4];       /* noise std per action component (first A used), >= 0    */
+  float lo, hi;         /* candidates are clipped to [lo, hi]; lo < hi            */
+  double lambda;        /* temperature, > 0 and finite                            */
+  double done_penalty;  /* >= 0; subtracted from a particle's score once its env
+                           has ended an episode                                   */
+  double ess_frac;      /* 0 .. 1; after a segment but the last, env e resamples
+                           iff ESS_e < ess_frac * C.  0 = never: no resample or
+                           select launch is issued at all                         */
+  uint64_t seed;
+} qs_smc_spec;
+
+typedef struct qs_smc_bufs {  /* device pointers owned by the planner             */
+  float* nominal;       /* [n][E][D][A]                                          */
+  float* candidates;    /* [n][C][E][D][A]  (what the advances read)             */
+  double* base;         /* [C][E]  the score a particle had when last resampled  */
+  double* weights;      /* [C][E]  normalised, of the last resample or finish    */
+  int32_t* parents;     /* [S][C][E] who particle c of env e was copied from
+                           after segment s (identity where nothing resampled)    */
+  int32_t* ancestors;   /* [S][C][E] whose actions the final particle c ran in
+                           segment s                                             */
+  double* ess;          /* [S][E]  effective sample size after segment s         */
+  double* offset;       /* [S][E]  the resampling offset u, 0 where not drawn    */
+  int32_t* resampled;   /* [S][E]  1 where env e resampled after segment s       */
+  int32_t* best;        /* [E]     the lowest c with the largest final weight    */
+  float* action;        /* [E][D][A] the first step of the updated nominal       */
+  uint64_t* tick;       /* [1]     device counter, +1 per finish                 */
+} qs_smc_bufs;
+
+typedef struct qs_smc qs_smc;
+
+int qs_smc_create(qs_handle* h, const qs_smc_spec* spec, qs_smc** out);
+int qs_smc_destroy(qs_smc* p);
+int qs_smc_buffers(const qs_smc* p, qs_smc_bufs* out);
+int qs_smc_branch(const qs_smc* p, qs_branch** out);
+int qs_smc_reset(qs_smc* p, const float* nominal, void* stream);
+int qs_smc_begin(qs_smc* p, void* stream);
+int qs_smc_sample(qs_smc* p, int segment, void* stream);
+int qs_smc_advance(qs_smc* p, int segment, void* stream);
+int qs_smc_resample(qs_smc* p, int segment, void* stream);
+int qs_smc_finish(qs_smc* p, void* stream);
+int qs_smc_plan(qs_smc* p, void* stream);
+
 /* Multi-step launches this handle has made so far (host, no device work):
  * out[0] on the general multi-step kernel instances, out[1] on the
  * shape-specialised one.  The specialised instance serves synthetic-policy

@@ -94,6 +94,21 @@ class QsCemBufs(ctypes.Structure):
                 ("iter_best", ctypes.c_void_p), ("action", ctypes.c_void_p), ("tick", ctypes.c_void_p)]
 
 
+class QsSmcSpec(ctypes.Structure):
+    """include/quadswarm.h qs_smc_spec: what a particle (SMC) planner is created from."""
+    _fields_ = [("horizon", ctypes.c_int32), ("segment", ctypes.c_int32), ("particles", ctypes.c_int32),
+                ("sigma", ctypes.c_float * 4), ("lo", ctypes.c_float), ("hi", ctypes.c_float),
+                ("lambda_", ctypes.c_double), ("done_penalty", ctypes.c_double), ("ess_frac", ctypes.c_double),
+                ("seed", ctypes.c_uint64)]
+
+
+class QsSmcBufs(ctypes.Structure):
+    """include/quadswarm.h qs_smc_bufs: the particle planner's device buffers."""
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        "nominal", "candidates", "base", "weights", "parents", "ancestors", "ess", "offset", "resampled", "best",
+        "action", "tick")]
+
+
 EPISODE_DTYPE = np.dtype([("ret", "<f8"), ("len", "<i4"), ("env", "<i4"), ("seq", "<i8")])
 
 # Every symbol include/quadswarm.h declares (tests check the .so exports them).
@@ -105,7 +120,9 @@ EXPORTS = ("qs_create", "qs_destroy", "qs_last_error", "qs_abi_version", "qs_get
            "qs_cem_refit", "qs_cem_finish", "qs_cem_plan", "qs_score_agents", "qs_pd_mppi_create", "qs_pd_mppi_ret_agent",
            "qs_pd_cem_create", "qs_pd_cem_ret_agent",
            "qs_branch_create", "qs_branch_destroy", "qs_branch_buffers", "qs_branch_steps", "qs_branch_fork",
-           "qs_branch_advance", "qs_branch_select", "qs_branch_state", "qs_launch_counts", "qs_ring_counts", "qs_state_io", "qs_episode_log", "qs_reset_error", "qs_calib_copy",
+           "qs_branch_advance", "qs_branch_select", "qs_branch_state",
+           "qs_smc_create", "qs_smc_destroy", "qs_smc_buffers", "qs_smc_branch", "qs_smc_reset", "qs_smc_begin",
+           "qs_smc_sample", "qs_smc_advance", "qs_smc_resample", "qs_smc_finish", "qs_smc_plan", "qs_launch_counts", "qs_ring_counts", "qs_state_io", "qs_episode_log", "qs_reset_error", "qs_calib_copy",
            # include/qs_learner.h
            "qs_gae", "qs_adam_gated", "qs_adam_commit", "qs_ppo_heads", "qs_ppo_heads_work_bytes",
            "qs_mlp_bias_tanh", "qs_mlp_bwd_blocks", "qs_mlp_tanh_bwd", "qs_mlp_sum_partials",
@@ -204,6 +221,18 @@ def load():
         L.qs_branch_advance.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(QsStepOut), vp]
         L.qs_branch_select.argtypes = [vp, vp, vp]
         L.qs_branch_state.argtypes = [vp, i32, vp, vp]
+    if hasattr(L, "qs_smc_create"):   # (a QS_DEV_LIB build from before the entry points: A/B runs)
+        L.qs_smc_create.argtypes = [vp, ctypes.POINTER(QsSmcSpec), ctypes.POINTER(vp)]
+        L.qs_smc_destroy.argtypes = [vp]
+        L.qs_smc_buffers.argtypes = [vp, ctypes.POINTER(QsSmcBufs)]
+        L.qs_smc_branch.argtypes = [vp, ctypes.POINTER(vp)]
+        L.qs_smc_reset.argtypes = [vp, vp, vp]
+        L.qs_smc_begin.argtypes = [vp, vp]
+        L.qs_smc_sample.argtypes = [vp, i32, vp]
+        L.qs_smc_advance.argtypes = [vp, i32, vp]
+        L.qs_smc_resample.argtypes = [vp, i32, vp]
+        L.qs_smc_finish.argtypes = [vp, vp]
+        L.qs_smc_plan.argtypes = [vp, vp]
     if hasattr(L, "qs_launch_counts"):   # (a QS_DEV_LIB build from before the entry point: A/B runs)
         L.qs_launch_counts.argtypes = [vp, ctypes.POINTER(i64)]
     if hasattr(L, "qs_ring_counts"):
@@ -274,7 +303,7 @@ def load():
     L.qs_rms_update.argtypes = [i64, ctypes.c_int32] + [vp] * 7
     L.qs_rms_normalize.argtypes = [i64, ctypes.c_int32, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp]
     for name in EXPORTS:
-        if (name in ("qs_launch_counts", "qs_ring_counts", "qs_score_depth", "qs_score") or name.startswith(("qs_mppi_", "qs_cem_", "qs_pd_", "qs_branch_"))
+        if (name in ("qs_launch_counts", "qs_ring_counts", "qs_score_depth", "qs_score") or name.startswith(("qs_mppi_", "qs_cem_", "qs_pd_", "qs_branch_", "qs_smc_"))
                 or name == "qs_score_agents") and not hasattr(L, name):
             continue   # (a QS_DEV_LIB build from before the entry point)
         if name not in ("qs_last_error", "qs_learner_last_error", "qs_rms_last_error", "qs_ppo_small_last_error",

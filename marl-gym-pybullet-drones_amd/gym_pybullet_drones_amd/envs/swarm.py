@@ -384,6 +384,24 @@ class QuadSwarm:
         self.__dict__.setdefault("_planners", weakref.WeakSet()).add(planner)   # close() ends them first
         return planner
 
+    def smc(self, horizon, particles, sigma, segment=None, lo=-1.0, hi=1.0, lam=1.0, done_penalty=0.0, ess_frac=0.5,
+            seed=0):
+        """An `SMCPlanner` on this swarm (qs_smc_create): `particles` branch rollouts
+        of `horizon` steps (any length: it is run in segments of `segment` steps,
+        1 .. score_depth(), by default min(horizon, score_depth())) forked from the
+        swarm's current state.  Each segment draws actions round the nominal with
+        per-component noise `sigma`, clipped to [lo, hi], advances the particles and
+        weighs them at temperature `lam`; an env whose effective sample size falls
+        below `ess_frac` * particles is resampled systematically (0: never, which
+        makes the tick a long-horizon MPPI tick).  The surviving particles' action
+        sequences are folded back into the nominal by their weights; `done_penalty`
+        is taken off a particle that ends an episode."""
+        if not hasattr(self.lib, "qs_smc_create"):
+            raise L.QuadSwarmError(f"{L.LIB_PATH} has no qs_smc_create: rebuild the HIP extension")
+        planner = SMCPlanner(self, horizon, particles, sigma, segment, lo, hi, lam, done_penalty, ess_frac, seed)
+        self.__dict__.setdefault("_planners", weakref.WeakSet()).add(planner)   # close() ends them first
+        return planner
+
     def launch_counts(self):
         """(general, hot): the multi-step launches made so far on the general kernel
         instances and on the shape-specialised one (qs_launch_counts; QS_HOT_SHAPE=0
@@ -600,8 +618,25 @@ class BranchSet:
             pass
 
 
+class _BranchView(BranchSet):
+    """A branch set that another object owns (`SMCPlanner.set`): the accumulators,
+    `steps` and `get_state` for reading; `close()` only lets go of it."""
+
+    def __init__(self, swarm, C, p):
+        self.swarm, self.lib, self.num_candidates = swarm, swarm.lib, int(C)
+        self._p = p
+        bufs = L.QsBranchBufs()
+        L.check(self.lib.qs_branch_buffers(self._p, ctypes.byref(bufs)), "qs_branch_buffers")
+        E, D = swarm.num_envs, swarm.num_drones
+        for name, shape, typestr in (("ret", (C, E), "<f8"), ("first_done", (C, E), "<i4"), ("ret_agent", (C, E, D), "<f8")):
+            setattr(self, name, torch.as_tensor(_DeviceSpan(getattr(bufs, name), shape, typestr), device=swarm.device))
+
+    def close(self):
+        self._p = ctypes.c_void_p()
+
+
 class _Planner:
-    """What `MPPIPlanner` and `CEMPlanner` share: creation through the entry
+    """What `MPPIPlanner`, `CEMPlanner` and `SMCPlanner` share: creation through the entry
     points `<_PREFIX>_*`, the device views, `plan`, `step_t` and `close`."""
 
     _PREFIX = None   # "qs_mppi" / "qs_cem"
@@ -799,3 +834,82 @@ class CEMPlanner(_Planner):
 
     def finish(self):
         self._call("finish")
+
+
+class SMCPlanner(_Planner):
+    """The native particle (sequential Monte Carlo) tick on a branch set (qs_smc_*,
+    include/quadswarm.h).
+
+    `begin()` forks the planner's own branch set from the swarm; for each segment
+    s of `segments` (a list of (start, length)), `sample(s)` draws the particles'
+    actions round `nominal` (particle 0 follows the nominal), `advance(s)` runs
+    them and `resample(s)` weighs the particles and, in every env whose effective
+    sample size is below ess_frac * particles, resamples them systematically into
+    `parents[s]` and gathers the branch set by it; `finish()` weighs the final
+    particles, traces their `ancestors` back through `parents`, writes the
+    weighted mean of their paths, shifted by one step, back to `nominal` and its
+    first step to `action`.  `plan()` is all of that.  Every call is a few
+    launches on the current stream with no host sync, and may be captured into a
+    graph together with the `step` that runs `action`.  With ess_frac = 0 nothing
+    is resampled: an MPPI tick whose horizon is not held to score_depth().
+
+    The buffers are torch tensors that view the planner's device memory (no
+    copies; they dangle after `close()`): nominal (n, E, D, A), candidates
+    (n, C, E, D, A), base and weights (C, E) float64, parents and ancestors
+    (S, C, E) int32, ess and offset (S, E) float64, resampled (S, E) int32, best
+    (E,) int32, action (E, D, A), tick (1,) (the uint64 counter, viewed as int64).
+    `set` is the planner's branch set for reading (`ret`, `first_done`,
+    `ret_agent`, `steps`, `get_state`); the planner owns it.  There is no
+    per-drone mode: the drones of an env share a branch's state.  The swarm must
+    outlive the planner."""
+
+    _PREFIX = "qs_smc"
+
+    def __init__(self, swarm, horizon, particles, sigma, segment=None, lo=-1.0, hi=1.0, lam=1.0, done_penalty=0.0,
+                 ess_frac=0.5, seed=0):
+        self._bind(swarm)
+        sig = self._per_component(sigma, "sigma")
+        if segment is None:
+            segment = min(int(horizon), swarm.score_depth())
+        spec = L.QsSmcSpec()
+        spec.horizon, spec.segment, spec.particles = int(horizon), int(segment), int(particles)
+        for a, s in enumerate(sig):
+            spec.sigma[a] = s
+        spec.lo, spec.hi, spec.lambda_, spec.done_penalty = float(lo), float(hi), float(lam), float(done_penalty)
+        spec.ess_frac, spec.seed = float(ess_frac), int(seed)
+        self.horizon, self.segment, self.num_particles = int(horizon), int(segment), int(particles)
+        n, Lseg, C, E, D, A = self.horizon, self.segment, self.num_particles, swarm.num_envs, swarm.num_drones, swarm.act_dim
+        self.segments = [(j, min(Lseg, n - j)) for j in range(0, n, Lseg)] if Lseg >= 1 else []
+        S = max(len(self.segments), 1)
+        self._create(spec, L.QsSmcBufs(), (
+            ("nominal", (n, E, D, A), "<f4"), ("candidates", (n, C, E, D, A), "<f4"), ("base", (C, E), "<f8"),
+            ("weights", (C, E), "<f8"), ("parents", (S, C, E), "<i4"), ("ancestors", (S, C, E), "<i4"),
+            ("ess", (S, E), "<f8"), ("offset", (S, E), "<f8"), ("resampled", (S, E), "<i4"), ("best", (E,), "<i4"),
+            ("action", (E, D, A), "<f4"), ("tick", (1,), "<i8")))
+        b = ctypes.c_void_p()
+        L.check(self.lib.qs_smc_branch(self._p, ctypes.byref(b)), "qs_smc_branch")
+        self.set = _BranchView(swarm, C, b)
+
+    def reset(self, nominal=None):
+        """Set the nominal sequence ((n, E, D, A) float32 on the device; None: zeros) and tick = 0."""
+        self._reset(nominal, "nominal")
+
+    def begin(self):
+        self._call("begin")
+
+    def sample(self, segment=0):
+        self._call("sample", int(segment))
+
+    def advance(self, segment=0):
+        self._call("advance", int(segment))
+
+    def resample(self, segment=0):
+        self._call("resample", int(segment))
+
+    def finish(self):
+        self._call("finish")
+
+    def close(self):
+        if getattr(self, "set", None) is not None:
+            self.set.close()
+        super().close()

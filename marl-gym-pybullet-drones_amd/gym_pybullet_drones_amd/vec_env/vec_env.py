@@ -261,6 +261,15 @@ class SwarmVecEnv(VecEnv):
         planner._stepper = self.step_t
         return planner
 
+    def smc(self, horizon, particles, sigma, **kw):
+        """An `SMCPlanner` on these envs (QuadSwarm.smc, same arguments).  Its
+        `step_t(**bufs)` is one receding-horizon tick: `plan()` from the envs'
+        current state, then `step_t(planner.action, **bufs)`, with step_t's
+        return; launches on the current stream, no host sync."""
+        planner = self.swarm.smc(horizon, particles, sigma, **kw)
+        planner._stepper = self.step_t
+        return planner
+
     # -------------------------------------------- checkpoint RNG (MP:203-270)
     def get_env_random_state(self):
         """Counter-based RNG: the stream state is (seed, per-env counters)."""
