@@ -476,6 +476,7 @@ int qs_branch_state(qs_branch* b, int block, void* buf, void* stream);
  *    candidates, ret and first_done as they are: a caller may fill them itself.
  *  - qs_mppi_plan = sample, qs_score(h, n, C, candidates, NULL, {ret,
  *    first_done}), update.  QS_E_STATE before qs_reset, with nothing launched.
+ *    (With a value attached the middle stage is qs_value_mppi_score, below.)
  *  - qs_mppi_reset copies `nominal` (device, [n][E][D][A]; NULL: zeros) into the
  *    planner and sets *tick = 0.  A new planner is in that state with zeros.
  *  - qs_mppi_create refusals (QS_E_INVALID, *out untouched): a handle with
@@ -560,7 +561,8 @@ int qs_mppi_plan(qs_mppi* p, void* stream);
  *    mean[n - 1] holds; *tick += 1 (once a tick, not once an iteration).
  *  - qs_cem_plan = begin, I × (sample(i), qs_score(h, n, C, candidates, NULL,
  *    {ret, first_done}), refit(i)), finish.  QS_E_STATE before qs_reset, with
- *    nothing launched.
+ *    nothing launched.  (With a value attached the scoring of every iteration is
+ *    qs_value_cem_score, below.)
  *  - qs_cem_reset copies `mean` (device, [n][E][D][A]; NULL: zeros) into the
  *    planner and sets *tick = 0.  A new planner is in that state with zeros.
  *  - qs_cem_sample / qs_cem_refit with an iteration outside 0 .. I - 1:
@@ -652,6 +654,88 @@ int qs_pd_mppi_create(qs_handle* h, const qs_mppi_spec* spec, qs_mppi** out);
 int qs_pd_mppi_ret_agent(const qs_mppi* p, double** out);
 int qs_pd_cem_create(qs_handle* h, const qs_cem_spec* spec, qs_cem** out);
 int qs_pd_cem_ret_agent(const qs_cem* p, double** out);
+
+/* Value tail: discounted, critic-bootstrapped returns for the MPPI and CEM ticks.
+ * (New entry points of ABI 4.)  With a value attached, a planner's score stage
+ * turns qs_score's undiscounted sum into the n-step bootstrapped return
+ *
+ *   G(c, e) = sum_{j <= jd} gamma^j · r_j  +  [first_done == n] · gamma^n · scale · V(s_n)
+ *
+ * where V is a tanh MLP with two hidden layers of `hidden` units and one output
+ * (the trainer's centralized critic) over the D · O concatenated obs of the env.
+ *
+ *  - The tail is ONE launch after the score launch, over the V = C · E virtual
+ *    envs: row v = c · E + e is last_obs[c][e][.][.], the obs the score launch wrote
+ *    for step n - 1 (post auto-reset; for a candidate that was never done it is
+ *    the true s_n).  With obs_mean / obs_var every input column i becomes
+ *    clamp((x - mean[i]) / sqrt(var[i] + eps), -clip, clip), evaluated in double
+ *    and rounded to float (qs_rms_normalize's expression).  H1 = tanh(X · W1^T +
+ *    b1), H2 = tanh(H1 · W2^T + b2), V = H2 · w3^T + b3 on the f32-input MFMA, the
+ *    activations kept on-chip.  The weights are torch nn.Linear tensors (w1
+ *    [hidden][in_dim], w2 [hidden][hidden], w3 [1][hidden], float32, contiguous),
+ *    read from the caller's pointers AT EVERY LAUNCH: there is no pack step, so a
+ *    critic updated in place is seen by the next tick and by a replayed graph.  The
+ *    caller keeps them alive while the value is attached.
+ *  - value[c][e] (float) is written for every row, whatever first_done says.
+ *  - The fold, in double, in place, with disc[0] = 1, disc[j] = disc[j - 1] · gamma
+ *    formed on the host and jd = first_done[c][e]: acc = 0; for j = 0 .. min(jd,
+ *    n - 1) in order acc = acc + disc[j] · (double) r_j[c][e]; if jd == n, acc = acc
+ *    + (disc[n] · scale) · (double) V; ret[c][e] = acc.  No multiply-add is
+ *    contracted.  With gamma = 1 no per-step rewards are requested and the sum is
+ *    the score launch's own ret: only the bootstrap term is added.  With gamma = 1
+ *    and no net there is nothing to do and nothing is launched.  No atomics and a
+ *    fixed summation order: the same inputs give the same bytes.
+ *  - A truncated candidate counts as ended, like a terminated one: its return
+ *    stops at the done step and it gets no bootstrap from terminal_obs.
+ *  - The critic must have been trained at the same norm_obs setting as the spec
+ *    (with the normaliser if obs_mean / obs_var are given, without it if not), and
+ *    `scale` undoes a reward normalisation the critic was trained under.
+ *  - Everything downstream reads ret as before: done_penalty still applies where
+ *    first_done < n.
+ *
+ * qs_value_tail is that launch on caller-owned buffers, bound to no handle (for
+ * callers who compose qs_score themselves).  last_obs [C][E][D][O] float and
+ * value_out [C][E] float are needed with a net; rewards is a host array of n
+ * device pointers, each [C][E] reals of real_bytes (4 or 8), needed with gamma !=
+ * 1 and not read otherwise; ret [C][E] double and first_done [C][E] int32 always.
+ * It runs on the current device.  1 <= n <= 32.
+ *
+ * qs_value_mppi_set / qs_value_cem_set copy the spec (NULL detaches the value)
+ * and allocate the planner's last_obs and value (with a net) and rewards
+ * [n][C][E] in the handle's precision (with gamma != 1); qs_value_*_buffers
+ * returns the three pointers, NULL where a buffer does not exist.  Both are host
+ * calls that may synchronise the device: do not capture them.  qs_value_mppi_score /
+ * qs_value_cem_score is the scoring stage of plan() as its own call, next to sample /
+ * update / refit: qs_score into the planner's ret / first_done, which with a value
+ * attached also names outs[n - 1].obs = last_obs and, for gamma != 1, outs[j].reward
+ * = rewards[j], followed by the tail.  Without a value it is exactly the qs_score
+ * call plan() made before.  QS_E_STATE before qs_reset.
+ *
+ * Refusals (QS_E_INVALID with a message; nothing is allocated and the planner is
+ * as it was): a per-drone planner (a centralized critic has one value per env);
+ * in_dim != D · O or > 1024; hidden outside {64, 128, 256}; a net that is partly
+ * NULL; one of obs_mean / obs_var without the other, or either without a net;
+ * gamma outside (0, 1]; a non-finite scale; last_obs (C · E · D · O · 4 bytes) past
+ * the 32-bit offsets.  The particle tick (qs_smc_*) takes no value: its weights
+ * are increments since the last resampling step.                                */
+typedef struct qs_value_spec {
+  int32_t in_dim;            /* I, must equal D · O of the handle, <= 1024            */
+  int32_t hidden;            /* N: 64, 128 or 256                                   */
+  const float *w1, *b1, *w2, *b2, *w3, *b3;   /* device; all NULL: no net (discount only) */
+  const double *obs_mean, *obs_var;           /* device [I], both or neither         */
+  double obs_eps, obs_clip;
+  double gamma;              /* 0 < gamma <= 1                                       */
+  double scale;              /* finite; multiplies V (reward-normalised critics)     */
+} qs_value_spec;
+
+int qs_value_tail(const qs_value_spec* spec, int n, int C, int E, int D, int O, int real_bytes, const float* last_obs,
+                  const void* const* rewards, double* ret, const int32_t* first_done, float* value_out, void* stream);
+int qs_value_mppi_set(qs_mppi* p, const qs_value_spec* spec);
+int qs_value_mppi_buffers(const qs_mppi* p, float** last_obs, float** value, void** rewards);
+int qs_value_mppi_score(qs_mppi* p, void* stream);
+int qs_value_cem_set(qs_cem* p, const qs_value_spec* spec);
+int qs_value_cem_buffers(const qs_cem* p, float** last_obs, float** value, void** rewards);
+int qs_value_cem_score(qs_cem* p, void* stream);
 
 /* Particle (sequential Monte Carlo) planner tick on top of a branch set: fork C
  * particles from the handle's current state, run the horizon in S = ceil(n / L)

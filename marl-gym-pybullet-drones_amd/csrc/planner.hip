@@ -299,11 +299,23 @@ int qs_mppi_update(qs_mppi* p, void* stream) {
   return update_impl(p, (hipStream_t)stream);
 }
 
+int qs_value_mppi_set(qs_mppi* p, const qs_value_spec* spec) { return qs::value_attach("qs_value_mppi_set", p, spec); }
+
+int qs_value_mppi_buffers(const qs_mppi* p, float** last_obs, float** value, void** rewards) {
+  return qs::value_buffers("qs_value_mppi_buffers", p, last_obs, value, rewards);
+}
+
+int qs_value_mppi_score(qs_mppi* p, void* stream) {
+  if (!p) return qs::set_last_error(QS_E_INVALID, "qs_value_mppi_score: null planner");
+  if (int rc = qs::planner_ready("qs_value_mppi_score", p)) return rc;
+  return qs::value_score(p, p->buf[qs::kMppiRet], p->buf[qs::kMppiFirstDone], stream);
+}
+
 int qs_mppi_plan(qs_mppi* p, void* stream) {
   if (!p) return qs::set_last_error(QS_E_INVALID, "qs_mppi_plan: null planner");
   if (int rc = qs::planner_ready("qs_mppi_plan", p)) return rc;
   if (int rc = sample_impl(p, (hipStream_t)stream)) return rc;
-  if (int rc = qs::planner_score(p, p->buf[qs::kMppiRet], p->buf[qs::kMppiFirstDone], stream)) return rc;
+  if (int rc = qs::value_score(p, p->buf[qs::kMppiRet], p->buf[qs::kMppiFirstDone], stream)) return rc;
   return update_impl(p, (hipStream_t)stream);
 }
 

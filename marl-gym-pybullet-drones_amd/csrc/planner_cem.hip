@@ -485,6 +485,18 @@ int qs_cem_finish(qs_cem* p, void* stream) {
   return finish_impl(p, (hipStream_t)stream);
 }
 
+int qs_value_cem_set(qs_cem* p, const qs_value_spec* spec) { return qs::value_attach("qs_value_cem_set", p, spec); }
+
+int qs_value_cem_buffers(const qs_cem* p, float** last_obs, float** value, void** rewards) {
+  return qs::value_buffers("qs_value_cem_buffers", p, last_obs, value, rewards);
+}
+
+int qs_value_cem_score(qs_cem* p, void* stream) {
+  if (!p) return qs::set_last_error(QS_E_INVALID, "qs_value_cem_score: null planner");
+  if (int rc = qs::planner_ready("qs_value_cem_score", p)) return rc;
+  return qs::value_score(p, p->buf[qs::kCemRet], p->buf[qs::kCemFirstDone], stream);
+}
+
 int qs_cem_plan(qs_cem* p, void* stream) {
   if (!p) return qs::set_last_error(QS_E_INVALID, "qs_cem_plan: null planner");
   if (int rc = qs::planner_ready("qs_cem_plan", p)) return rc;
@@ -492,7 +504,7 @@ int qs_cem_plan(qs_cem* p, void* stream) {
   if (int rc = begin_impl(p, st)) return rc;
   for (int i = 0; i < p->spec.iterations; ++i) {
     if (int rc = sample_impl(p, i, st)) return rc;
-    if (int rc = qs::planner_score(p, p->buf[qs::kCemRet], p->buf[qs::kCemFirstDone], stream)) return rc;
+    if (int rc = qs::value_score(p, p->buf[qs::kCemRet], p->buf[qs::kCemFirstDone], stream)) return rc;
     if (int rc = refit_impl(p, i, st)) return rc;
   }
   return finish_impl(p, st);

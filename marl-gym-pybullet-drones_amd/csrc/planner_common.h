@@ -1,7 +1,8 @@
 // planner_common.h — what the MPPI tick (planner.hip) and the CEM tick
 // (planner_cem.hip) share: the sample kernel, the penalised score, the row
 // reduction of the per-workgroup variants, and the host record with its create /
-// destroy / reset / score plumbing.  HIP; included by those two files only.
+// destroy / reset / score plumbing.  HIP; included by the planner files only
+// (planner_value.hip, the value tail of the score stage, among them).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -121,6 +122,8 @@ __device__ __forceinline__ void block_row_reduce(double acc, double* part, int t
 }
 
 // ---- host --------------------------------------------------------------------------
+struct ValueState;   // planner_value.hip: the attached value's spec copy and buffers
+
 // What qs_mppi and qs_cem both are.  The derived records add `spec`, `variant`,
 // `grids`, `bytes[]` and `buf[]`.
 struct PlannerBase {
@@ -135,6 +138,7 @@ struct PlannerBase {
   bool per_drone = false;
   void* ret_agent = nullptr;         // [C][E][D] doubles, per-drone mode only
   uint64_t ret_agent_bytes = 0;
+  ValueState* value = nullptr;       // qs_value_mppi_set / qs_value_cem_set; null: the plain score
   int units() const { return per_drone ? E * D : E; }      // what the kernels take for envs
   int row() const { return per_drone ? A : D * A; }        // components of a unit's row
   int fd_div() const { return per_drone ? D : 1; }         // units per entry of first_done
@@ -191,11 +195,21 @@ int planner_too_large(const char* who, T* p) {
                                                          "offsets of qs_score, at most 2^27 candidates)");
 }
 
+// The value tail (planner_value.hip).  value_attach copies the spec and allocates
+// last_obs / value / rewards (a null spec detaches); value_score is the score stage:
+// planner_score, and with a value attached the qs_score launch that also names the
+// last obs and the per-step rewards, then the tail.
+void value_release(PlannerBase* p);
+int value_attach(const char* who, PlannerBase* p, const qs_value_spec* spec);
+int value_buffers(const char* who, const PlannerBase* p, float** last_obs, float** value, void** rewards);
+int value_score(PlannerBase* p, void* ret, void* first_done, void* stream);
+
 template <class T>
 void planner_free(T* p) {
   for (void* b : p->buf)
     if (b) (void)hipFree(b);
   if (p->ret_agent) (void)hipFree(p->ret_agent);
+  value_release(p);
 }
 
 // Allocates and zeroes every buffer of p->bytes (and ret_agent where

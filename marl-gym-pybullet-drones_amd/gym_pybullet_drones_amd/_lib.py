@@ -94,6 +94,15 @@ class QsCemBufs(ctypes.Structure):
                 ("iter_best", ctypes.c_void_p), ("action", ctypes.c_void_p), ("tick", ctypes.c_void_p)]
 
 
+class QsValueSpec(ctypes.Structure):
+    """include/quadswarm.h qs_value_spec: the critic, normaliser and discount of a value tail."""
+    _fields_ = [("in_dim", ctypes.c_int32), ("hidden", ctypes.c_int32),
+                ("w1", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+                ("w3", ctypes.c_void_p), ("b3", ctypes.c_void_p), ("obs_mean", ctypes.c_void_p),
+                ("obs_var", ctypes.c_void_p), ("obs_eps", ctypes.c_double), ("obs_clip", ctypes.c_double),
+                ("gamma", ctypes.c_double), ("scale", ctypes.c_double)]
+
+
 class QsSmcSpec(ctypes.Structure):
     """include/quadswarm.h qs_smc_spec: what a particle (SMC) planner is created from."""
     _fields_ = [("horizon", ctypes.c_int32), ("segment", ctypes.c_int32), ("particles", ctypes.c_int32),
@@ -119,6 +128,8 @@ EXPORTS = ("qs_create", "qs_destroy", "qs_last_error", "qs_abi_version", "qs_get
            "qs_mppi_plan", "qs_cem_create", "qs_cem_destroy", "qs_cem_buffers", "qs_cem_reset", "qs_cem_begin", "qs_cem_sample",
            "qs_cem_refit", "qs_cem_finish", "qs_cem_plan", "qs_score_agents", "qs_pd_mppi_create", "qs_pd_mppi_ret_agent",
            "qs_pd_cem_create", "qs_pd_cem_ret_agent",
+           "qs_value_tail", "qs_value_mppi_set", "qs_value_mppi_buffers", "qs_value_mppi_score", "qs_value_cem_set",
+           "qs_value_cem_buffers", "qs_value_cem_score",
            "qs_branch_create", "qs_branch_destroy", "qs_branch_buffers", "qs_branch_steps", "qs_branch_fork",
            "qs_branch_advance", "qs_branch_select", "qs_branch_state",
            "qs_smc_create", "qs_smc_destroy", "qs_smc_buffers", "qs_smc_branch", "qs_smc_reset", "qs_smc_begin",
@@ -212,6 +223,13 @@ def load():
         L.qs_pd_mppi_ret_agent.argtypes = [vp, ctypes.POINTER(vp)]
         L.qs_pd_cem_create.argtypes = [vp, ctypes.POINTER(QsCemSpec), ctypes.POINTER(vp)]
         L.qs_pd_cem_ret_agent.argtypes = [vp, ctypes.POINTER(vp)]
+    if hasattr(L, "qs_value_tail"):   # (a QS_DEV_LIB build from before the entry points: A/B runs)
+        L.qs_value_tail.argtypes = [ctypes.POINTER(QsValueSpec), i32, i32, i32, i32, i32, i32, vp, ctypes.POINTER(vp), vp,
+                                    vp, vp, vp]
+        for who in ("mppi", "cem"):
+            getattr(L, f"qs_value_{who}_set").argtypes = [vp, ctypes.POINTER(QsValueSpec)]
+            getattr(L, f"qs_value_{who}_buffers").argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
+            getattr(L, f"qs_value_{who}_score").argtypes = [vp, vp]
     if hasattr(L, "qs_branch_create"):   # (a QS_DEV_LIB build from before the entry points: A/B runs)
         L.qs_branch_create.argtypes = [vp, i32, ctypes.POINTER(vp)]
         L.qs_branch_destroy.argtypes = [vp]
@@ -304,7 +322,7 @@ def load():
     L.qs_rms_normalize.argtypes = [i64, ctypes.c_int32, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp]
     for name in EXPORTS:
         if (name in ("qs_launch_counts", "qs_ring_counts", "qs_score_depth", "qs_score") or name.startswith(("qs_mppi_", "qs_cem_", "qs_pd_", "qs_branch_", "qs_smc_"))
-                or name == "qs_score_agents") and not hasattr(L, name):
+                or name == "qs_score_agents" or name.startswith("qs_value_")) and not hasattr(L, name):
             continue   # (a QS_DEV_LIB build from before the entry point)
         if name not in ("qs_last_error", "qs_learner_last_error", "qs_rms_last_error", "qs_ppo_small_last_error",
                         "qs_rollout_last_error"):
@@ -331,7 +349,7 @@ def check(rc, what=""):
             msg = lib.qs_rollout_last_error()
         elif what.startswith(("qs_ppo_small", "qs_ppo_critic", "qs_wgrad_t")):
             msg = lib.qs_ppo_small_last_error()
-        elif what.startswith(("qs_gae", "qs_adam", "qs_ppo", "qs_mlp", "qs_wgrad", "qs_value")):
+        elif what.startswith(("qs_gae", "qs_adam", "qs_ppo", "qs_mlp", "qs_wgrad", "qs_value_head")):
             msg = lib.qs_learner_last_error()
         else:
             msg = lib.qs_last_error()

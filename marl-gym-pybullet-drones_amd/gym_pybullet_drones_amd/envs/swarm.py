@@ -719,7 +719,120 @@ class _Planner:
             pass
 
 
-class MPPIPlanner(_Planner):
+def value_spec(critic=None, gamma=1.0, scale=1.0, obs_normalizer=None, device=None):
+    """The `QsValueSpec` of a value tail (include/quadswarm.h qs_value_spec) and the
+    tensors it points into, which the caller keeps alive as long as the spec is used.
+
+    critic: None (discount only), a `CentralizedCritic`, an `MLP` with two hidden
+    layers, tanh and one output, or the six tensors (w1, b1, w2, b2, w3, b3) in
+    nn.Linear's layout.  obs_normalizer: a `MeanStdNormalizer`, whose `rms.mean` /
+    `rms.var` (float64), `clip` and `epsilon` are used.  Every tensor must be
+    contiguous, of the right dtype and on `device`; nothing is copied, so a critic
+    that training updates in place is read as it is at every launch."""
+    spec, keep = L.QsValueSpec(), []
+    spec.gamma, spec.scale = float(gamma), float(scale)
+
+    def dev_ptr(t, dtype, what):
+        if (not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda
+                or (device is not None and t.device != device)):
+            raise ValueError(f"{what} must be a contiguous {dtype} tensor on {device if device is not None else 'the GPU'}")
+        keep.append(t)
+        return t.data_ptr()
+
+    if critic is not None:
+        net = getattr(critic, "v_net", critic)
+        if isinstance(net, (tuple, list)):
+            if len(net) != 6:
+                raise ValueError("critic: a tuple must hold the six tensors (w1, b1, w2, b2, w3, b3)")
+            w1, b1, w2, b2, w3, b3 = net
+        else:
+            fcs = getattr(net, "fcs", None)
+            if fcs is None or len(fcs) != 3 or not getattr(net, "_tanh3", False) or fcs[2].out_features != 1:
+                raise ValueError("critic must be a CentralizedCritic, an MLP with two hidden layers, tanh and one "
+                                 "output, or a tuple of six tensors")
+            if getattr(critic, "include_actions", False):
+                raise ValueError("critic: a critic that takes actions (include_actions) has no value of an obs alone")
+            w1, b1, w2, b2, w3, b3 = (t.detach() for fc in fcs for t in (fc.weight, fc.bias))
+        for t in (w1, b1, w2, b2, w3, b3):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("critic: the weights must be torch tensors")
+        N, I = tuple(w1.shape) if w1.dim() == 2 else (0, 0)
+        if (w1.dim() != 2 or tuple(b1.shape) != (N,) or tuple(w2.shape) != (N, N) or tuple(b2.shape) != (N,)
+                or w3.numel() != N or w3.dim() not in (1, 2) or b3.numel() != 1):
+            raise ValueError("critic: shapes must be w1 (N, I), b1 (N,), w2 (N, N), b2 (N,), w3 (1, N), b3 (1,)")
+        spec.in_dim, spec.hidden = int(I), int(N)
+        for name, t in zip(("w1", "b1", "w2", "b2", "w3", "b3"), (w1, b1, w2, b2, w3, b3)):
+            setattr(spec, name, dev_ptr(t, torch.float32, f"critic {name}"))
+    if obs_normalizer is not None:
+        rms = obs_normalizer.rms
+        mean, var = rms.mean.reshape(-1), rms.var.reshape(-1)   # (views: contiguous statistics stay shared)
+        if critic is not None and mean.numel() != spec.in_dim:
+            raise ValueError(f"obs_normalizer has {mean.numel()} columns, the critic takes {spec.in_dim}")
+        spec.obs_mean, spec.obs_var = dev_ptr(mean, torch.float64, "obs_normalizer.rms.mean"), dev_ptr(
+            var, torch.float64, "obs_normalizer.rms.var")
+        spec.obs_eps, spec.obs_clip = float(obs_normalizer.epsilon), float(obs_normalizer.clip)
+        keep.append(obs_normalizer)
+    keep.append(critic)
+    return spec, keep
+
+
+class _ValueTail:
+    """What `MPPIPlanner` and `CEMPlanner` add for discounted, critic-bootstrapped
+    returns (qs_value_mppi_* / qs_value_cem_*: set, buffers, score; include/quadswarm.h)."""
+
+    last_obs = value = rewards = None   # the views, while a value is attached and the buffer exists
+    _value_keep = None
+
+    def _need(self, name):
+        fn = f"qs_value_{self._PREFIX[3:]}_{name}"
+        if not hasattr(self.lib, fn):
+            raise L.QuadSwarmError(f"{L.LIB_PATH} has no {fn}: rebuild the HIP extension")
+        return fn
+
+    def set_value(self, critic=None, gamma=1.0, scale=1.0, obs_normalizer=None):
+        """Attach a value to the score stage: `ret` becomes the discounted rewards
+        up to the candidate's first done step plus, where it was never done,
+        gamma^n · scale · critic(last obs).  See `value_spec` for the arguments; the
+        planner keeps the tensors alive.  Afterwards `last_obs` (C, E, D, O) float32
+        and `value` (C, E) float32 (with a critic) and `rewards` (n, C, E) in the
+        swarm's precision (with gamma != 1) view the planner's buffers; each is None
+        where its buffer does not exist.  A host call: not to be captured.  A
+        refusal (ValueError / QuadSwarmError) leaves the planner as it was."""
+        sw = self.swarm
+        spec, keep = value_spec(critic, gamma, scale, obs_normalizer, device=sw.device)
+        fn = self._need("set")
+        with torch.cuda.device(sw.device):
+            L.check(getattr(self.lib, fn)(self._p, ctypes.byref(spec)), fn)
+        self._value_keep = keep
+        self._value_views()
+
+    def clear_value(self):
+        """Detach the value: the planner scores by the plain sum of rewards again."""
+        fn = self._need("set")
+        with torch.cuda.device(self.swarm.device):
+            L.check(getattr(self.lib, fn)(self._p, None), fn)
+        self._value_keep = None
+        self._value_views()
+
+    def _value_views(self):
+        sw, fn = self.swarm, self._need("buffers")
+        ptrs = [ctypes.c_void_p() for _ in range(3)]
+        L.check(getattr(self.lib, fn)(self._p, *[ctypes.byref(p) for p in ptrs]), fn)
+        n, C, E, D, O = self.horizon, self.num_candidates, sw.num_envs, sw.num_drones, sw.obs_dim
+        shapes = (("last_obs", (C, E, D, O), "<f4"), ("value", (C, E), "<f4"),
+                  ("rewards", (n, C, E), "<f8" if sw.rdtype == torch.float64 else "<f4"))
+        for p, (name, shape, typestr) in zip(ptrs, shapes):
+            setattr(self, name, torch.as_tensor(_DeviceSpan(p.value, shape, typestr), device=sw.device) if p.value else None)
+
+    def score(self):
+        """The scoring stage of `plan()` on its own: the candidates are run from the
+        swarm's current state into `ret` / `first_done` (and, with a value attached,
+        `last_obs`, `rewards`, `value` and the folded `ret`)."""
+        fn = self._need("score")
+        L.check(getattr(self.lib, fn)(self._p, self._stream()), fn)
+
+
+class MPPIPlanner(_ValueTail, _Planner):
     """The native MPPI tick round `QuadSwarm.score` (qs_mppi_*, include/quadswarm.h).
 
     `sample()` draws `candidates` sequences round `nominal` (candidate 0 is the
@@ -742,7 +855,12 @@ class MPPIPlanner(_Planner):
     copies its own best candidate's slice.  ret is about ret_agent.sum(-1) / D, so
     a per-drone `lam` or `done_penalty` is on a scale D times the env-level one;
     with downwash or contacts a drone's return also depends on the others'
-    actions and the factored weighting is an approximation."""
+    actions and the factored weighting is an approximation.
+
+    `set_value(critic, gamma, scale, obs_normalizer)` (env-level planners only)
+    makes `ret` the discounted return bootstrapped with the trainer's critic
+    behind the horizon, in one more launch after the score launch; `score()` is
+    that stage on its own and `clear_value()` undoes it (`_ValueTail`)."""
 
     _PREFIX = "qs_mppi"
 
@@ -774,7 +892,7 @@ class MPPIPlanner(_Planner):
         self._call("update")
 
 
-class CEMPlanner(_Planner):
+class CEMPlanner(_ValueTail, _Planner):
     """The native CEM tick round `QuadSwarm.score` (qs_cem_*, include/quadswarm.h).
 
     `begin()` restarts the spread `std` at sigma; `sample(i)` draws `candidates`
@@ -796,7 +914,10 @@ class CEMPlanner(_Planner):
     per_drone=True (qs_pd_cem_create): every drone ranks the candidates by its own
     return, `ret_agent` (C, E, D) float64, less `done_penalty` where its env ends,
     and refits its own A components; elites is then (K, E, D) and iter_best
-    (I, E, D).  The scale and the caveat are `MPPIPlanner`'s."""
+    (I, E, D).  The scale and the caveat are `MPPIPlanner`'s.
+
+    `set_value`, `score()` and `clear_value()` are `MPPIPlanner`'s: with a value
+    attached every iteration's scoring is followed by the value tail."""
 
     _PREFIX = "qs_cem"
 
