@@ -737,6 +737,91 @@ int qs_value_cem_set(qs_cem* p, const qs_value_spec* spec);
 int qs_value_cem_buffers(const qs_cem* p, float** last_obs, float** value, void** rewards);
 int qs_value_cem_score(qs_cem* p, void* stream);
 
+/* Policy prior of the MPPI and CEM ticks: `count` = K of a planner's C candidates
+ * per env are closed-loop rollouts of the trainer's actor from the handle's
+ * current state, so that the ordinary weighting / ranking decides among them and
+ * the sampled candidates and the plan is never worse, on the model, than the
+ * policy.  (New entry points of ABI 4, like qs_value_*.)
+ *
+ *  - The actor launch is ONE launch over the R = K · E · D rows of a step: row
+ *    r = (k · E + e) · D + d reads its O = in_dim floats of obs (with bcast != 0
+ *    from row r mod (E · D): the caller's [E][D][O] obs for every trajectory).
+ *    With obs_mean / obs_var (the trainer's normaliser over an env's [D][O] obs:
+ *    D · O entries) column i of drone d becomes clamp((x - mean[d · O + i]) /
+ *    sqrt(var[d · O + i] + eps), -clip, clip), evaluated in double and rounded to
+ *    float (qs_rms_normalize's expression).  H1 = tanh(X · W1^T + b1), H2 = tanh(H1 ·
+ *    W2^T + b2) on the f32-input MFMA, the activations kept on-chip, out = H2 ·
+ *    W3^T in float in a fixed order, mean = action_scale · (out + b3).  Trajectory
+ *    k >= 1 adds std_scale · exp(logstd[a]) · z_a, z the Box-Muller normals of
+ *    qs_mppi_sample drawn from Philox4x32-10(key = seed, counter = (tick, genv0 +
+ *    e, k · 32 + j, (7 << 24) | d)); trajectory 0 is the mode.  The result is
+ *    clipped to [lo, hi] and stored to actions_out[k][e][d][.]; the raw obs row is
+ *    copied to obs_seen[k][e][d][.] (NULL: no copy; it must not be obs_in).
+ *  - The weights are torch nn.Linear tensors (w1 [hidden][in_dim], w2
+ *    [hidden][hidden], w3 [act_dim][hidden], logstd [act_dim], float32,
+ *    contiguous).  They, logstd and the statistics are read from the caller's
+ *    pointers AT EVERY LAUNCH: there is no pack step, so an actor updated in place
+ *    is seen by the next tick and by a replayed graph.  The caller keeps them, and
+ *    `obs`, alive while the prior is attached.  No atomics: the same inputs give
+ *    the same bytes.
+ *  - qs_prior_act is that launch for step j on caller-owned buffers, bound to no
+ *    handle (spec->obs and spec->count are not read: obs_in and K are).  tick:
+ *    device uint64, read as qs_mppi_sample reads the planner's.  It runs on the
+ *    current device.  0 <= j < 32, D <= 256.
+ *  - qs_prior_mppi_set / qs_prior_cem_set copy the spec (NULL detaches the prior),
+ *    create a branch set of K candidates that the planner owns and allocate
+ *    prior_actions [n][K][E][D][A] and prior_obs [n][K][E][D][O] (float32);
+ *    qs_prior_*_buffers returns the two pointers, NULL without a prior.  Both are
+ *    host calls that may synchronise the device: do not capture them.
+ *  - qs_prior_mppi_rollout / qs_prior_cem_rollout is the prior stage on its own:
+ *    qs_branch_fork of the planner's set, then for j = 0 .. n - 1 the actor launch
+ *    reading obs slot j (step 0: spec->obs, broadcast, and copied to slot 0) and
+ *    writing prior_actions[j], and for j < n - 1 a one-step qs_branch_advance with
+ *    prior_actions[j] whose obs output is slot j + 1: 2 n launches, stream-ordered,
+ *    no host sync, capturable, keyed on the planner's seed, the global env id and
+ *    the device tick counter, clipped to the planner's [lo, hi].  spec->obs is the
+ *    caller's [E][D][O] obs of the handle's current state (the buffer it passes as
+ *    qs_step_out.obs, and qs_reset's obs at first), read at every tick and never
+ *    copied.  The handle is not changed.  QS_E_STATE before qs_reset or without a
+ *    prior.
+ *  - With a prior attached qs_mppi_plan runs the stage first and qs_cem_plan runs
+ *    it once per tick after begin, and every qs_mppi_sample / qs_cem_sample is
+ *    followed by one inject launch that copies prior_actions[j] over candidates
+ *    C - K .. C - 1 of step j.  Candidate 0 stays the nominal / mean; score, value
+ *    tail, update / refit and the per-drone variants are unchanged.  Without a
+ *    prior a planner launches and writes exactly what it did before.
+ *
+ * Refusals (QS_E_INVALID with a message; nothing is allocated and the planner is
+ * as it was): count outside 1 .. C - 1; a net (w1 .. b3, logstd) that is partly
+ * NULL; hidden outside {64, 128, 256}; in_dim != obs_dim or > 1024; act_dim != the
+ * handle's; one of obs_mean / obs_var without the other; a NULL obs; std_scale not
+ * finite or negative, action_scale not finite; a step's obs (K · E · D · O · 4 bytes)
+ * past the 32-bit offsets; what qs_branch_create refuses.  The particle tick
+ * (qs_smc_*) takes no prior: its particles are resampled mid-horizon, which a
+ * closed-loop trajectory fixed before the tick cannot follow.                    */
+typedef struct qs_prior_spec {
+  int32_t in_dim;            /* O, must equal obs_dim of the handle, <= 1024         */
+  int32_t hidden;            /* N: 64, 128 or 256                                   */
+  int32_t act_dim;           /* A, must equal act_dim of the handle, <= 4            */
+  const float *w1, *b1, *w2, *b2, *w3, *b3;   /* device; the actor's pi_net          */
+  const float* logstd;       /* device [A]                                          */
+  float action_scale;        /* finite; multiplies the net's output                 */
+  float std_scale;           /* finite, >= 0; multiplies exp(logstd) (0: no noise)   */
+  const double *obs_mean, *obs_var;           /* device [D · O], both or neither     */
+  double obs_eps, obs_clip;
+  int32_t count;             /* K: 1 .. candidates - 1 prior candidates per env      */
+  const float* obs;          /* device [E][D][O]: the obs of the handle's state      */
+} qs_prior_spec;
+
+int qs_prior_act(const qs_prior_spec* spec, int j, int K, int E, int D, float lo, float hi, uint64_t seed, int64_t genv0,
+                 const uint64_t* tick, const float* obs_in, int bcast, float* actions_out, float* obs_seen, void* stream);
+int qs_prior_mppi_set(qs_mppi* p, const qs_prior_spec* spec);
+int qs_prior_mppi_buffers(const qs_mppi* p, float** prior_actions, float** prior_obs);
+int qs_prior_mppi_rollout(qs_mppi* p, void* stream);
+int qs_prior_cem_set(qs_cem* p, const qs_prior_spec* spec);
+int qs_prior_cem_buffers(const qs_cem* p, float** prior_actions, float** prior_obs);
+int qs_prior_cem_rollout(qs_cem* p, void* stream);
+
 /* Particle (sequential Monte Carlo) planner tick on top of a branch set: fork C
  * particles from the handle's current state, run the horizon in S = ceil(n / L)
  * segments of at most L steps, each "sample actions, advance the particles, weigh
@@ -820,7 +905,9 @@ int qs_value_cem_score(qs_cem* p, void* stream);
  *    qs_branch_create refuses (a handle with qs_score_depth(h) = 0 among it), and
  *    sizes beyond the 32-bit offsets of a branch advance or S · C · E >= 2^31.
  *    qs_smc_sample / advance / resample with s outside 0 .. S - 1: QS_E_INVALID,
- *    nothing launched.                                                          */
+ *    nothing launched.
+ *  - No policy prior (qs_prior_*): the particles are resampled mid-horizon, which
+ *    a closed-loop trajectory fixed before the tick cannot follow.              */
 typedef struct qs_smc_spec {
   int32_t horizon;      /* n >= 1 steps per tick; S = ceil(n / segment) <= 256     */
   int32_t segment;      /* L: 1 .. qs_score_depth(h) steps per advance; the last

@@ -2,7 +2,9 @@
 // qs_mppi_*; DESIGN.md §4a "Planner tick").
 //
 // Three kernels round the one qs_score launch: planner_sample_kernel (shared with
-// the CEM tick, planner_common.h) perturbs the nominal sequence into C candidates,
+// the CEM tick, planner_common.h) perturbs the nominal sequence into C candidates
+// (with a policy prior attached, planner_prior.hip, the last of them are then
+// overwritten with the actor's closed-loop rollouts),
 // mppi_weights_* turns qs_score's ret / first_done into softmax weights per env,
 // and mppi_sum_* folds the candidates back into the nominal, shifted by one step.
 // Everything per env is summed in double in a fixed order (no atomics), the tick
@@ -216,7 +218,13 @@ int sample_impl(qs_mppi* p, hipStream_t st) {
   hipLaunchKernelGGL(qs::planner_sample_kernel<SigmaArg>, dim3(p->grids.sample, (uint32_t)p->n), dim3(qs::kMppiThreads), 0,
                      st, P);
   PLANNER_HIP_TRY(hipGetLastError());
-  return QS_OK;
+  return qs::prior_inject(p, P.cand, st);   // (nothing without a prior)
+}
+
+// The prior stage, keyed as the sample is.
+int prior_impl(qs_mppi* p, void* stream) {
+  return qs::prior_rollout("qs_prior_mppi_rollout", p, p->spec.seed, (const uint64_t*)p->buf[qs::kMppiTick], p->spec.lo,
+                           p->spec.hi, stream);
 }
 
 int update_impl(qs_mppi* p, hipStream_t st) {
@@ -311,9 +319,23 @@ int qs_value_mppi_score(qs_mppi* p, void* stream) {
   return qs::value_score(p, p->buf[qs::kMppiRet], p->buf[qs::kMppiFirstDone], stream);
 }
 
+int qs_prior_mppi_set(qs_mppi* p, const qs_prior_spec* spec) { return qs::prior_attach("qs_prior_mppi_set", p, spec); }
+
+int qs_prior_mppi_buffers(const qs_mppi* p, float** prior_actions, float** prior_obs) {
+  return qs::prior_buffers("qs_prior_mppi_buffers", p, prior_actions, prior_obs);
+}
+
+int qs_prior_mppi_rollout(qs_mppi* p, void* stream) {
+  if (!p) return qs::set_last_error(QS_E_INVALID, "qs_prior_mppi_rollout: null planner");
+  if (int rc = qs::planner_ready("qs_prior_mppi_rollout", p)) return rc;
+  return prior_impl(p, stream);
+}
+
 int qs_mppi_plan(qs_mppi* p, void* stream) {
   if (!p) return qs::set_last_error(QS_E_INVALID, "qs_mppi_plan: null planner");
   if (int rc = qs::planner_ready("qs_mppi_plan", p)) return rc;
+  if (p->prior)
+    if (int rc = prior_impl(p, stream)) return rc;
   if (int rc = sample_impl(p, (hipStream_t)stream)) return rc;
   if (int rc = qs::value_score(p, p->buf[qs::kMppiRet], p->buf[qs::kMppiFirstDone], stream)) return rc;
   return update_impl(p, (hipStream_t)stream);

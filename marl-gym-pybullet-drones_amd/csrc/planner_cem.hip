@@ -1,7 +1,9 @@
 // planner_cem.hip — the CEM planner tick on top of qs_score (include/quadswarm.h,
 // qs_cem_*; DESIGN.md §4a "CEM tick").
 //
-// A tick is begin, I × (sample, qs_score, refit), finish.  The sample is
+// A tick is begin, I × (sample, qs_score, refit), finish (with a policy prior
+// attached, planner_prior.hip: begin, the prior stage, and every sample followed by
+// the inject launch).  The sample is
 // planner_sample_kernel (shared with the MPPI tick, planner_common.h) with a
 // per-element spread and the iteration in the Philox counter; cem_select_* ranks
 // an env's candidates by their penalised
@@ -339,7 +341,13 @@ int sample_impl(qs_cem* p, int iteration, hipStream_t st) {
   hipLaunchKernelGGL(qs::planner_sample_kernel<StdMem>, dim3(p->grids.sample, (uint32_t)p->n), dim3(qs::kCemThreads), 0, st,
                      P);
   PLANNER_HIP_TRY(hipGetLastError());
-  return QS_OK;
+  return qs::prior_inject(p, P.cand, st);   // (nothing without a prior)
+}
+
+// The prior stage, keyed as the sample is: once per tick, whatever the iteration.
+int prior_impl(qs_cem* p, void* stream) {
+  return qs::prior_rollout("qs_prior_cem_rollout", p, p->spec.seed, (const uint64_t*)p->buf[qs::kCemTick], p->spec.lo,
+                           p->spec.hi, stream);
 }
 
 int refit_impl(qs_cem* p, int iteration, hipStream_t st) {
@@ -497,11 +505,25 @@ int qs_value_cem_score(qs_cem* p, void* stream) {
   return qs::value_score(p, p->buf[qs::kCemRet], p->buf[qs::kCemFirstDone], stream);
 }
 
+int qs_prior_cem_set(qs_cem* p, const qs_prior_spec* spec) { return qs::prior_attach("qs_prior_cem_set", p, spec); }
+
+int qs_prior_cem_buffers(const qs_cem* p, float** prior_actions, float** prior_obs) {
+  return qs::prior_buffers("qs_prior_cem_buffers", p, prior_actions, prior_obs);
+}
+
+int qs_prior_cem_rollout(qs_cem* p, void* stream) {
+  if (!p) return qs::set_last_error(QS_E_INVALID, "qs_prior_cem_rollout: null planner");
+  if (int rc = qs::planner_ready("qs_prior_cem_rollout", p)) return rc;
+  return prior_impl(p, stream);
+}
+
 int qs_cem_plan(qs_cem* p, void* stream) {
   if (!p) return qs::set_last_error(QS_E_INVALID, "qs_cem_plan: null planner");
   if (int rc = qs::planner_ready("qs_cem_plan", p)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (int rc = begin_impl(p, st)) return rc;
+  if (p->prior)
+    if (int rc = prior_impl(p, stream)) return rc;
   for (int i = 0; i < p->spec.iterations; ++i) {
     if (int rc = sample_impl(p, i, st)) return rc;
     if (int rc = qs::value_score(p, p->buf[qs::kCemRet], p->buf[qs::kCemFirstDone], stream)) return rc;

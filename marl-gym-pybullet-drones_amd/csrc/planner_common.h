@@ -2,7 +2,8 @@
 // (planner_cem.hip) share: the sample kernel, the penalised score, the row
 // reduction of the per-workgroup variants, and the host record with its create /
 // destroy / reset / score plumbing.  HIP; included by the planner files only
-// (planner_value.hip, the value tail of the score stage, among them).
+// (planner_value.hip, the value tail of the score stage, and planner_prior.hip, the
+// policy prior, among them).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -123,6 +124,7 @@ __device__ __forceinline__ void block_row_reduce(double acc, double* part, int t
 
 // ---- host --------------------------------------------------------------------------
 struct ValueState;   // planner_value.hip: the attached value's spec copy and buffers
+struct PriorState;   // planner_prior.hip: the attached policy prior's spec copy, branch set and buffers
 
 // What qs_mppi and qs_cem both are.  The derived records add `spec`, `variant`,
 // `grids`, `bytes[]` and `buf[]`.
@@ -139,6 +141,7 @@ struct PlannerBase {
   void* ret_agent = nullptr;         // [C][E][D] doubles, per-drone mode only
   uint64_t ret_agent_bytes = 0;
   ValueState* value = nullptr;       // qs_value_mppi_set / qs_value_cem_set; null: the plain score
+  PriorState* prior = nullptr;       // qs_prior_mppi_set / qs_prior_cem_set; null: every candidate is sampled
   int units() const { return per_drone ? E * D : E; }      // what the kernels take for envs
   int row() const { return per_drone ? A : D * A; }        // components of a unit's row
   int fd_div() const { return per_drone ? D : 1; }         // units per entry of first_done
@@ -204,12 +207,25 @@ int value_attach(const char* who, PlannerBase* p, const qs_value_spec* spec);
 int value_buffers(const char* who, const PlannerBase* p, float** last_obs, float** value, void** rewards);
 int value_score(PlannerBase* p, void* ret, void* first_done, void* stream);
 
+// The policy prior (planner_prior.hip).  prior_attach copies the spec, creates the
+// planner's branch set of `count` candidates and allocates prior_actions /
+// prior_obs (a null spec detaches); prior_rollout is the prior stage: fork, then
+// per step the actor launch and, but for the last step, a one-step advance;
+// prior_inject copies prior_actions over the last `count` candidates of every
+// step, and launches nothing without a prior.
+void prior_release(PlannerBase* p);
+int prior_attach(const char* who, PlannerBase* p, const qs_prior_spec* spec);
+int prior_buffers(const char* who, const PlannerBase* p, float** prior_actions, float** prior_obs);
+int prior_rollout(const char* who, PlannerBase* p, uint64_t seed, const uint64_t* tick, float lo, float hi, void* stream);
+int prior_inject(PlannerBase* p, float* candidates, void* stream);
+
 template <class T>
 void planner_free(T* p) {
   for (void* b : p->buf)
     if (b) (void)hipFree(b);
   if (p->ret_agent) (void)hipFree(p->ret_agent);
   value_release(p);
+  prior_release(p);
 }
 
 // Allocates and zeroes every buffer of p->bytes (and ret_agent where

@@ -7,22 +7,19 @@
 // with the activations kept in LDS between the layers, write value[c][e], and
 // fold the discounted rewards and the bootstrap term into ret[c][e] in float64.
 // The weights are read from the caller's nn.Linear tensors at every launch (no
-// pack step), W1 and W2 streamed through LDS in K-chunks.  No atomics and a fixed
+// pack step), W1 and W2 streamed through LDS in K-chunks (mlp_tile.h, shared with
+// the policy prior).  No atomics and a fixed
 // summation order: the same inputs give the same bytes.  The host arithmetic
 // (refusals, sizes, tile, grid, LDS plan, discount table) is value_sizes.h.
 #include "planner_common.h"
-#include "value_sizes.h"
+#include "mlp_tile.h"
 
 namespace {
 
 using qs::kValueChunk;
-using qs::kValueMfmaK;
 using qs::kValueMfmaM;
 using qs::kValuePad;
 using qs::kValueThreads;
-using qs::kValueWaves;
-
-typedef float value_f4 __attribute__((ext_vector_type(4)));
 
 struct FoldParams {
   double* ret;                               // [V], rewritten in place
@@ -66,129 +63,45 @@ __global__ __launch_bounds__(kValueThreads) void value_fold_kernel(FoldParams F,
   if (v < (uint32_t)V) fold_row(F, v, false, 0.0f);
 }
 
-// out = clip((x − mean) / sqrt(var + eps), ±clip) in float64, rounded to float32:
-// rms_norm1 of normalizer.hip.
-__device__ __forceinline__ float norm1(float xv, double m, double sd, double clip) {
-  double y = ((double)xv - m) / sd;
-  y = y < -clip ? -clip : (y > clip ? clip : y);
-  return (float)y;
-}
-
-// One layer's product for a workgroup's rows: acc[mt][nt] += A · Wᵀ over K, with W
-// [N][K] row-major in global memory streamed through sW in chunks of kValueChunk
-// columns (zero beyond K).  FIRST: A is the input, staged (and normalised) a chunk
-// at a time into sX; otherwise A is sH, resident.  Wave w owns the column tiles
-// w · NT .. w · NT + NT - 1 of all MT row tiles.  The next chunk's global loads are
-// issued before the current chunk's MFMAs and land in LDS after them.
-template <int N, int MT, bool FIRST>
-__device__ __forceinline__ void layer_product(const ValueParams& P, const float* __restrict__ W, int K, size_t row0,
-                                              float* sH, float* sW, float* sX, value_f4 (&acc)[MT][N / 64]) {
-  constexpr int NT = N / 64, TM = MT * kValueMfmaM, CP = kValueChunk + kValuePad, HP = N + kValuePad;
-  constexpr int WR = N / 8, XR = TM / 8;   // rows of W / X a thread stages per chunk (32 columns x 8 rows a pass)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int col = tid & 31, rsub = tid >> 5;   // this thread's column of a chunk, and its first row
-  const int l15 = lane & 15, lq = lane >> 4;
-  float wreg[WR], xreg[FIRST ? XR : 1];
-  const int chunks = (K + kValueChunk - 1) / kValueChunk;
-
-  auto load = [&](int ch) {
-    const int k = ch * kValueChunk + col;
-    const bool kv = k < K;
+// The rows of last_obs as the critic takes them (mlp_tile.h, layer_product's
+// input): column k normalised by entry k of the statistics.
+struct ValueInput {
+  const float* x;                            // [rows][I]
+  const double *mean, *var;
+  double eps, clip;
+  size_t rows;
+  int I;
+  template <int XR>
+  __device__ __forceinline__ void stage(size_t r0, int k, bool kv, float (&out)[XR]) const {
+    double m = 0.0, sd = 1.0;
+    if (mean && kv) {
+      m = mean[k];
+      sd = sqrt(var[k] + eps);
+    }
 #pragma unroll
-    for (int i = 0; i < WR; ++i) wreg[i] = kv ? W[(size_t)(rsub + 8 * i) * K + k] : 0.0f;
-    if constexpr (FIRST) {
-      double m = 0.0, sd = 1.0;
-      if (P.mean && kv) {
-        m = P.mean[k];
-        sd = sqrt(P.var[k] + P.eps);
+    for (int i = 0; i < XR; ++i) {
+      const size_t r = r0 + (size_t)(8 * i);
+      float xv = 0.0f;
+      if (kv && r < rows) {
+        xv = x[r * (size_t)I + k];
+        if (mean) xv = qs::norm1(xv, m, sd, clip);
       }
-#pragma unroll
-      for (int i = 0; i < XR; ++i) {
-        const size_t r = row0 + (size_t)(rsub + 8 * i);
-        float xv = 0.0f;
-        if (kv && r < (size_t)P.V) {
-          xv = P.x[r * (size_t)K + k];
-          if (P.mean) xv = norm1(xv, m, sd, P.clip);
-        }
-        xreg[i] = xv;
-      }
+      out[i] = xv;
     }
-  };
-
-  load(0);
-  for (int ch = 0; ch < chunks; ++ch) {
-#pragma unroll
-    for (int i = 0; i < WR; ++i) sW[(rsub + 8 * i) * CP + col] = wreg[i];
-    if constexpr (FIRST) {
-#pragma unroll
-      for (int i = 0; i < XR; ++i) sX[(rsub + 8 * i) * CP + col] = xreg[i];
-    }
-    __syncthreads();
-    if (ch + 1 < chunks) load(ch + 1);
-    const int left = K - ch * kValueChunk;
-    const int ksteps = left >= kValueChunk ? kValueChunk / kValueMfmaK : (left + kValueMfmaK - 1) / kValueMfmaK;
-    const float* A = FIRST ? sX : sH + ch * kValueChunk;
-    constexpr int AP = FIRST ? CP : HP;
-    for (int ks = 0; ks < ksteps; ++ks) {
-      const int kk = ks * kValueMfmaK + lq;
-      float a[MT], b[NT];
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) a[mt] = A[(mt * kValueMfmaM + l15) * AP + kk];
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) b[nt] = sW[((wave * NT + nt) * kValueMfmaM + l15) * CP + kk];
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mt], b[nt], acc[mt][nt], 0, 0, 0);
-    }
-    __syncthreads();   // sW / sX are rewritten by the next trip (and sH by the caller)
   }
-}
+};
 
-// The accumulators' (row, column) of register r: row = 4 · (lane >> 4) + r, column = lane & 15.
 template <int N, int MT>
 __global__ __launch_bounds__(kValueThreads) void value_mlp_kernel(ValueParams P) {
-  constexpr int NT = N / 64, TM = MT * kValueMfmaM, CP = kValueChunk + kValuePad, HP = N + kValuePad;
+  constexpr int TM = MT * kValueMfmaM, CP = kValueChunk + kValuePad, HP = N + kValuePad;
   __shared__ float sH[TM * HP];
   __shared__ float sW[N * CP];
   __shared__ float sX[TM * CP];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, lq = lane >> 4;
+  const int tid = threadIdx.x;
   const size_t row0 = (size_t)blockIdx.x * TM;
-  value_f4 acc[MT][NT];
-  auto clear = [&]() {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = value_f4{0.0f, 0.0f, 0.0f, 0.0f};
-  };
-
-  // H1 = tanh(X · W1ᵀ + b1) into sH
-  clear();
-  layer_product<N, MT, true>(P, P.w1, P.I, row0, sH, sW, sX, acc);
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int nc = (wave * NT + nt) * kValueMfmaM + l15;
-    const float bias = P.b1[nc];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sH[(mt * kValueMfmaM + 4 * lq + r) * HP + nc] = tanhf(acc[mt][nt][r] + bias);
-  }
-  __syncthreads();
-
-  // H2 = tanh(H1 · W2ᵀ + b2); sH becomes H2 · w3, column by column
-  clear();
-  layer_product<N, MT, false>(P, P.w2, N, row0, sH, sW, sX, acc);   // (ends in a barrier: every wave is done with H1)
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int nc = (wave * NT + nt) * kValueMfmaM + l15;
-    const float bias = P.b2[nc], w3 = P.w3[nc];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sH[(mt * kValueMfmaM + 4 * lq + r) * HP + nc] = tanhf(acc[mt][nt][r] + bias) * w3;
-  }
-  __syncthreads();
+  // sH = tanh(tanh(X · W1ᵀ + b1) · W2ᵀ + b2) · w3, column by column
+  const ValueInput in{P.x, P.mean, P.var, P.eps, P.clip, (size_t)P.V, P.I};
+  qs::hidden_layers<N, MT>(in, P.I, P.w1, P.b1, P.w2, P.b2, P.w3, row0, sH, sW, sX);
 
   // V = Σ_n sH[row][n] + b3: eight lanes a row, each over n = part, part + 8, ..., then an xor tree
   if (tid < TM * 8) {   // (whole waves: TM · 8 is 128 or 256)

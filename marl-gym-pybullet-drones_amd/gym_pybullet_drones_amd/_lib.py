@@ -103,6 +103,16 @@ class QsValueSpec(ctypes.Structure):
                 ("gamma", ctypes.c_double), ("scale", ctypes.c_double)]
 
 
+class QsPriorSpec(ctypes.Structure):
+    """include/quadswarm.h qs_prior_spec: the actor, normaliser, count and obs of a policy prior."""
+    _fields_ = [("in_dim", ctypes.c_int32), ("hidden", ctypes.c_int32), ("act_dim", ctypes.c_int32),
+                ("w1", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+                ("w3", ctypes.c_void_p), ("b3", ctypes.c_void_p), ("logstd", ctypes.c_void_p),
+                ("action_scale", ctypes.c_float), ("std_scale", ctypes.c_float), ("obs_mean", ctypes.c_void_p),
+                ("obs_var", ctypes.c_void_p), ("obs_eps", ctypes.c_double), ("obs_clip", ctypes.c_double),
+                ("count", ctypes.c_int32), ("obs", ctypes.c_void_p)]
+
+
 class QsSmcSpec(ctypes.Structure):
     """include/quadswarm.h qs_smc_spec: what a particle (SMC) planner is created from."""
     _fields_ = [("horizon", ctypes.c_int32), ("segment", ctypes.c_int32), ("particles", ctypes.c_int32),
@@ -130,6 +140,8 @@ EXPORTS = ("qs_create", "qs_destroy", "qs_last_error", "qs_abi_version", "qs_get
            "qs_pd_cem_create", "qs_pd_cem_ret_agent",
            "qs_value_tail", "qs_value_mppi_set", "qs_value_mppi_buffers", "qs_value_mppi_score", "qs_value_cem_set",
            "qs_value_cem_buffers", "qs_value_cem_score",
+           "qs_prior_act", "qs_prior_mppi_set", "qs_prior_mppi_buffers", "qs_prior_mppi_rollout", "qs_prior_cem_set",
+           "qs_prior_cem_buffers", "qs_prior_cem_rollout",
            "qs_branch_create", "qs_branch_destroy", "qs_branch_buffers", "qs_branch_steps", "qs_branch_fork",
            "qs_branch_advance", "qs_branch_select", "qs_branch_state",
            "qs_smc_create", "qs_smc_destroy", "qs_smc_buffers", "qs_smc_branch", "qs_smc_reset", "qs_smc_begin",
@@ -230,6 +242,13 @@ def load():
             getattr(L, f"qs_value_{who}_set").argtypes = [vp, ctypes.POINTER(QsValueSpec)]
             getattr(L, f"qs_value_{who}_buffers").argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
             getattr(L, f"qs_value_{who}_score").argtypes = [vp, vp]
+    if hasattr(L, "qs_prior_act"):   # (a QS_DEV_LIB build from before the entry points: A/B runs)
+        L.qs_prior_act.argtypes = [ctypes.POINTER(QsPriorSpec), i32, i32, i32, i32, ctypes.c_float, ctypes.c_float,
+                                   ctypes.c_uint64, i64, vp, vp, i32, vp, vp, vp]
+        for who in ("mppi", "cem"):
+            getattr(L, f"qs_prior_{who}_set").argtypes = [vp, ctypes.POINTER(QsPriorSpec)]
+            getattr(L, f"qs_prior_{who}_buffers").argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
+            getattr(L, f"qs_prior_{who}_rollout").argtypes = [vp, vp]
     if hasattr(L, "qs_branch_create"):   # (a QS_DEV_LIB build from before the entry points: A/B runs)
         L.qs_branch_create.argtypes = [vp, i32, ctypes.POINTER(vp)]
         L.qs_branch_destroy.argtypes = [vp]
@@ -322,7 +341,7 @@ def load():
     L.qs_rms_normalize.argtypes = [i64, ctypes.c_int32, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp]
     for name in EXPORTS:
         if (name in ("qs_launch_counts", "qs_ring_counts", "qs_score_depth", "qs_score") or name.startswith(("qs_mppi_", "qs_cem_", "qs_pd_", "qs_branch_", "qs_smc_"))
-                or name == "qs_score_agents" or name.startswith("qs_value_")) and not hasattr(L, name):
+                or name == "qs_score_agents" or name.startswith(("qs_value_", "qs_prior_"))) and not hasattr(L, name):
             continue   # (a QS_DEV_LIB build from before the entry point)
         if name not in ("qs_last_error", "qs_learner_last_error", "qs_rms_last_error", "qs_ppo_small_last_error",
                         "qs_rollout_last_error"):

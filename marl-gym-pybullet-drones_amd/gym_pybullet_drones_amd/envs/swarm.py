@@ -832,7 +832,135 @@ class _ValueTail:
         L.check(getattr(self.lib, fn)(self._p, self._stream()), fn)
 
 
-class MPPIPlanner(_ValueTail, _Planner):
+def prior_spec(actor, count, obs, obs_normalizer=None, std_scale=1.0, device=None, action_scale=None):
+    """The `QsPriorSpec` of a policy prior (include/quadswarm.h qs_prior_spec) and the
+    tensors it points into, which the caller keeps alive as long as the spec is used.
+
+    actor: an `MLPActor` (its `pi_net`, two hidden tanh layers, its `logstd` and
+    `action_scale`), a `MAPPOActorCritic` (its `.actor`), or the seven tensors (w1, b1,
+    w2, b2, w3, b3, logstd) in nn.Linear's layout with `action_scale` (default 1).
+    count: the prior candidates per env.  obs: the contiguous (E, D, O) float32 obs of
+    the swarm's current state.  obs_normalizer: the trainer's `MeanStdNormalizer` over
+    an env's (D, O) obs, whose `rms.mean` / `rms.var` (float64), `clip` and `epsilon`
+    are used.  std_scale multiplies exp(logstd) (0: every prior candidate is the
+    mode).  Every tensor must be contiguous, of the right dtype and on `device`;
+    nothing is copied, so an actor that training updates in place is read as it is
+    at every launch."""
+    spec, keep = L.QsPriorSpec(), []
+
+    def dev_ptr(t, dtype, what):
+        if (not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda
+                or (device is not None and t.device != device)):
+            raise ValueError(f"{what} must be a contiguous {dtype} tensor on {device if device is not None else 'the GPU'}")
+        keep.append(t)
+        return t.data_ptr()
+
+    net = getattr(actor, "actor", actor)
+    if isinstance(net, (tuple, list)):
+        if len(net) != 7:
+            raise ValueError("actor: a tuple must hold the seven tensors (w1, b1, w2, b2, w3, b3, logstd)")
+        w1, b1, w2, b2, w3, b3, logstd = net
+        scale = 1.0 if action_scale is None else action_scale
+    else:
+        pi = getattr(net, "pi_net", None)
+        fcs = getattr(pi, "fcs", None)
+        if fcs is None or len(fcs) != 3 or not getattr(pi, "_tanh3", False) or not hasattr(net, "logstd"):
+            raise ValueError("actor must be an MLPActor with two hidden tanh layers, a MAPPOActorCritic or a tuple of "
+                             "seven tensors")
+        w1, b1, w2, b2, w3, b3 = (t.detach() for fc in fcs for t in (fc.weight, fc.bias))
+        logstd = net.logstd.detach()
+        scale = net.action_scale if action_scale is None else action_scale
+    for t in (w1, b1, w2, b2, w3, b3, logstd):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("actor: the weights must be torch tensors")
+    N, I = tuple(w1.shape) if w1.dim() == 2 else (0, 0)
+    A = w3.shape[0] if w3.dim() == 2 else 0
+    if (w1.dim() != 2 or tuple(b1.shape) != (N,) or tuple(w2.shape) != (N, N) or tuple(b2.shape) != (N,)
+            or tuple(w3.shape) != (A, N) or tuple(b3.shape) != (A,) or tuple(logstd.shape) != (A,)):
+        raise ValueError("actor: shapes must be w1 (N, I), b1 (N,), w2 (N, N), b2 (N,), w3 (A, N), b3 (A,), logstd (A,)")
+    spec.in_dim, spec.hidden, spec.act_dim, spec.count = int(I), int(N), int(A), int(count)
+    for name, t in zip(("w1", "b1", "w2", "b2", "w3", "b3", "logstd"), (w1, b1, w2, b2, w3, b3, logstd)):
+        setattr(spec, name, dev_ptr(t, torch.float32, f"actor {name}"))
+    spec.action_scale, spec.std_scale = float(scale), float(std_scale)
+    if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[2] != I:
+        raise ValueError(f"obs must be the (num_envs, num_drones, {I}) obs of the swarm's current state")
+    spec.obs = dev_ptr(obs, torch.float32, "obs")
+    if obs_normalizer is not None:
+        rms = obs_normalizer.rms
+        mean, var = rms.mean.reshape(-1), rms.var.reshape(-1)   # (views: contiguous statistics stay shared)
+        if mean.numel() != obs.shape[1] * I or var.numel() != mean.numel():
+            raise ValueError(f"obs_normalizer has {mean.numel()} entries, an env's obs {obs.shape[1]} x {I}")
+        spec.obs_mean, spec.obs_var = dev_ptr(mean, torch.float64, "obs_normalizer.rms.mean"), dev_ptr(
+            var, torch.float64, "obs_normalizer.rms.var")
+        spec.obs_eps, spec.obs_clip = float(obs_normalizer.epsilon), float(obs_normalizer.clip)
+        keep.append(obs_normalizer)
+    keep.append(actor)
+    return spec, keep
+
+
+class _PolicyPrior:
+    """What `MPPIPlanner` and `CEMPlanner`, env-level and per-drone alike, add for a
+    policy prior (qs_prior_mppi_* / qs_prior_cem_*: set, buffers, rollout;
+    include/quadswarm.h)."""
+
+    prior_actions = prior_obs = None   # the views, while a prior is attached
+    _prior_keep = None
+
+    def _prior_fn(self, name):
+        fn = f"qs_prior_{self._PREFIX[3:]}_{name}"
+        if not hasattr(self.lib, fn):
+            raise L.QuadSwarmError(f"{L.LIB_PATH} has no {fn}: rebuild the HIP extension")
+        return fn
+
+    def set_prior(self, actor, count, obs, obs_normalizer=None, std_scale=1.0, action_scale=None):
+        """Make the last `count` candidates of every env closed-loop rollouts of
+        `actor` from the swarm's current state: the first is the policy's mode,
+        the others add std_scale · exp(logstd) noise, all clipped to [lo, hi].
+        `obs` is the contiguous (E, D, O) float32 tensor that always holds the obs
+        of the swarm's current state (the one passed as obs= to `step` / `step_t`);
+        it is read at every tick and not copied.  See `prior_spec` for the other
+        arguments; the planner keeps the tensors alive.  Afterwards `prior_actions`
+        (n, count, E, D, A) and `prior_obs` (n, count, E, D, O) view the planner's
+        buffers: slot j of `prior_obs` is the obs the actor saw at step j.  A host
+        call: not to be captured.  A refusal (ValueError / QuadSwarmError) leaves
+        the planner as it was."""
+        sw = self.swarm
+        spec, keep = prior_spec(actor, count, obs, obs_normalizer, std_scale, device=sw.device, action_scale=action_scale)
+        if tuple(obs.shape) != (sw.num_envs, sw.num_drones, sw.obs_dim):
+            raise ValueError(f"obs must be ({sw.num_envs}, {sw.num_drones}, {sw.obs_dim}), the swarm's obs")
+        fn = self._prior_fn("set")
+        with torch.cuda.device(sw.device):
+            L.check(getattr(self.lib, fn)(self._p, ctypes.byref(spec)), fn)
+        self._prior_keep = keep
+        self._prior_views(int(count))
+
+    def clear_prior(self):
+        """Detach the prior: every candidate but the first is sampled again."""
+        fn = self._prior_fn("set")
+        with torch.cuda.device(self.swarm.device):
+            L.check(getattr(self.lib, fn)(self._p, None), fn)
+        self._prior_keep = None
+        self._prior_views(0)
+
+    def _prior_views(self, K):
+        sw, fn = self.swarm, self._prior_fn("buffers")
+        ptrs = [ctypes.c_void_p() for _ in range(2)]
+        L.check(getattr(self.lib, fn)(self._p, *[ctypes.byref(p) for p in ptrs]), fn)
+        n, E, D = self.horizon, sw.num_envs, sw.num_drones
+        for p, name, last in zip(ptrs, ("prior_actions", "prior_obs"), (sw.act_dim, sw.obs_dim)):
+            setattr(self, name,
+                    torch.as_tensor(_DeviceSpan(p.value, (n, K, E, D, last), "<f4"), device=sw.device) if p.value else None)
+
+    def prior(self):
+        """The prior stage of `plan()` on its own: the actor's `count` closed-loop
+        rollouts from the swarm's current state into `prior_actions` / `prior_obs`
+        (2 · horizon launches, no host sync).  The next `sample()` copies them over
+        the last `count` candidates."""
+        fn = self._prior_fn("rollout")
+        L.check(getattr(self.lib, fn)(self._p, self._stream()), fn)
+
+
+class MPPIPlanner(_PolicyPrior, _ValueTail, _Planner):
     """The native MPPI tick round `QuadSwarm.score` (qs_mppi_*, include/quadswarm.h).
 
     `sample()` draws `candidates` sequences round `nominal` (candidate 0 is the
@@ -860,7 +988,13 @@ class MPPIPlanner(_ValueTail, _Planner):
     `set_value(critic, gamma, scale, obs_normalizer)` (env-level planners only)
     makes `ret` the discounted return bootstrapped with the trainer's critic
     behind the horizon, in one more launch after the score launch; `score()` is
-    that stage on its own and `clear_value()` undoes it (`_ValueTail`)."""
+    that stage on its own and `clear_value()` undoes it (`_ValueTail`).
+
+    `set_prior(actor, count, obs, obs_normalizer, std_scale)` makes the last
+    `count` candidates closed-loop rollouts of the trainer's actor, which
+    `plan()` forms before it samples (2 · horizon launches more); `prior()` is
+    that stage on its own, `prior_actions` / `prior_obs` its results and
+    `clear_prior()` undoes it (`_PolicyPrior`)."""
 
     _PREFIX = "qs_mppi"
 
@@ -892,7 +1026,7 @@ class MPPIPlanner(_ValueTail, _Planner):
         self._call("update")
 
 
-class CEMPlanner(_ValueTail, _Planner):
+class CEMPlanner(_PolicyPrior, _ValueTail, _Planner):
     """The native CEM tick round `QuadSwarm.score` (qs_cem_*, include/quadswarm.h).
 
     `begin()` restarts the spread `std` at sigma; `sample(i)` draws `candidates`
@@ -917,7 +1051,10 @@ class CEMPlanner(_ValueTail, _Planner):
     (I, E, D).  The scale and the caveat are `MPPIPlanner`'s.
 
     `set_value`, `score()` and `clear_value()` are `MPPIPlanner`'s: with a value
-    attached every iteration's scoring is followed by the value tail."""
+    attached every iteration's scoring is followed by the value tail.
+    `set_prior`, `prior()` and `clear_prior()` are `MPPIPlanner`'s too: the prior
+    stage runs once per tick, after `begin()`, and every iteration's `sample(i)`
+    ends with the actor's rollouts as its last `count` candidates."""
 
     _PREFIX = "qs_cem"
 
@@ -981,7 +1118,9 @@ class SMCPlanner(_Planner):
     (E,) int32, action (E, D, A), tick (1,) (the uint64 counter, viewed as int64).
     `set` is the planner's branch set for reading (`ret`, `first_done`,
     `ret_agent`, `steps`, `get_state`); the planner owns it.  There is no
-    per-drone mode: the drones of an env share a branch's state.  The swarm must
+    per-drone mode: the drones of an env share a branch's state, and no policy
+    prior (`MPPIPlanner.set_prior`): the particles are resampled mid-horizon, which
+    a closed-loop trajectory fixed before the tick cannot follow.  The swarm must
     outlive the planner."""
 
     _PREFIX = "qs_smc"
