@@ -4,7 +4,8 @@ every input of one qs_ppo_small_grads call, and a float64 autograd restatement
 of the losses (compute_policy_loss / compute_value_loss, AG:602-683) through
 the whole nets.  Plain torch with a `device` argument: the reference half runs
 on the CPU, and the data (drawn from seeded CPU generators) is the same on
-every device.
+every device.  tests/direct_grads_case.py builds the direct iteration's cases
+from the same pieces (make_agent, draw, losses, check_against_float64).
 
 Old log-probabilities lie 0.25·noise from the current ones, so 30-50 % of the
 rows are outside the clip bounds (both branches of the tile kernel's PPO head,
@@ -93,21 +94,28 @@ def actor_rows(case, idx):
     return (idx[:, None] * case.D + torch.arange(case.D, device=idx.device)[None, :]).reshape(-1)
 
 
-def build(mb, D, O, A, action_scale, seed, T_E, device, w1p=True):
-    """The nets as MAPPOAgent(hidden_dim=256, small=True) builds them (inside
-    FlatBuffers), their qs_mlp256 structs, and the inputs of one minibatch of
-    mb env-timesteps out of a table of T_E > mb."""
-    from gym_pybullet_drones_amd import _lib as L
-    from gym_pybullet_drones_amd.mappo.agent import MAPPOAgent, _mlp256
+def make_agent(D, O, A, action_scale, seed, device, hidden_dim=256, **agent_kw):
+    """MAPPOAgent with the cases' loss settings, its weights drawn from `seed`
+    (the same on every device and for every keyword) and logstd spread over
+    -0.7 .. -0.3; the spaces it was built for as .obs_space / .act_space."""
+    from gym_pybullet_drones_amd.mappo.agent import MAPPOAgent
     from gym_pybullet_drones_amd.utils.spaces import Box
-    assert T_E > mb
     obs_space = Box(-np.inf * np.ones((D, O)), np.inf * np.ones((D, O)))
     act_space = Box(-np.ones((D, A)), np.ones((D, A)))
+    agent_kw.setdefault("use_graphs", False)
     torch.manual_seed(seed)
-    agent = MAPPOAgent(obs_space, act_space, hidden_dim=256, entropy_coef=ENT_COEF, clip_param=CLIP,
-                       action_scale=action_scale, use_graphs=False, device=device, small=True)
+    agent = MAPPOAgent(obs_space, act_space, hidden_dim=hidden_dim, entropy_coef=ENT_COEF, clip_param=CLIP,
+                       action_scale=action_scale, device=device, **agent_kw)
     with torch.no_grad():
         agent.ac.actor.logstd.copy_(torch.linspace(-0.7, -0.3, A))
+    return agent
+
+
+def draw(agent, mb, D, O, A, action_scale, seed, T_E, device):
+    """The inputs of one minibatch of mb env-timesteps out of a table of
+    T_E > mb, from a CPU generator seeded with `seed`; the old
+    log-probabilities from the float64 copy of `agent`'s actor."""
+    assert T_E > mb
     g = torch.Generator().manual_seed(seed)
     dev = torch.device(device)
     case = types.SimpleNamespace(mb=mb, D=D, O=O, A=A, scale=float(action_scale), seed=seed, T_E=T_E, device=dev,
@@ -133,6 +141,19 @@ def build(mb, D, O, A, action_scale, seed, T_E, device, w1p=True):
                             torch.full_like(ratio, bound + GUARD_SHIFT))
         logp_old = torch.where(near, logp64 - torch.log(moved), logp_old)
     case.logp_old = logp_old.float()
+    case._ref, case._e32 = {}, {}
+    return case
+
+
+def build(mb, D, O, A, action_scale, seed, T_E, device, w1p=True):
+    """The nets as MAPPOAgent(hidden_dim=256, small=True) builds them (inside
+    FlatBuffers), their qs_mlp256 structs, and the inputs of one minibatch of
+    mb env-timesteps out of a table of T_E > mb."""
+    from gym_pybullet_drones_amd import _lib as L
+    from gym_pybullet_drones_amd.mappo.agent import _mlp256
+    agent = make_agent(D, O, A, action_scale, seed, device, small=True)
+    case = draw(agent, mb, D, O, A, action_scale, seed, T_E, device)
+    dev = case.device
     # the path's own copies: W2ᵀ of both nets and (w1p) W1 padded to whole 16-column quads
     mlps = (agent.ac.actor.pi_net, agent.ac.critic.v_net)
     case.w2t = [m.fcs[1].weight.detach().t().contiguous() for m in mlps]
@@ -144,7 +165,6 @@ def build(mb, D, O, A, action_scale, seed, T_E, device, w1p=True):
     case.nets = (_mlp256(agent.actor_opt, mlps[0], agent.ac.actor.logstd, case.w2t[0], L.QsMlp256,
                          case.w1p[0] if w1p else None),
                  _mlp256(agent.critic_opt, mlps[1], None, case.w2t[1], L.QsMlp256, case.w1p[1] if w1p else None))
-    case._ref = {}
     return case
 
 
@@ -161,10 +181,12 @@ def get_case(i, device):
     return _built[key]
 
 
-def losses(case, idx, dtype, logp_old=None):
+def losses(case, idx, dtype, logp_old=None, clamp=True):
     """compute_policy_loss / compute_value_loss (AG:602-683) restated over the
     whole nets in `dtype` with autograd: the gradients of policy + ent_coef ·
-    entropy + value by every parameter, the losses and the per-row terms."""
+    entropy + value by every parameter, the losses and the per-row terms.
+    clamp=False: the policy loss without its clipped term (a fault the tests'
+    metric must see, never the reference)."""
     p = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in param_tensors(case).items()}
     rows = actor_rows(case, idx)
     lpo = (case.logp_old if logp_old is None else logp_old)[rows].to(dtype)
@@ -172,7 +194,7 @@ def losses(case, idx, dtype, logp_old=None):
                  case.act.reshape(-1, case.A)[rows].to(dtype))
     adv = case.adv_env[idx].to(dtype).repeat_interleave(case.D)
     ratio = torch.exp(logp - lpo)
-    min_term = torch.min(ratio * adv, torch.clamp(ratio, 1.0 - CLIP, 1.0 + CLIP) * adv)
+    min_term = torch.min(ratio * adv, torch.clamp(ratio, 1.0 - CLIP, 1.0 + CLIP) * adv) if clamp else ratio * adv
     policy = -min_term.mean()
     ent = (0.5 + 0.5 * math.log(2 * math.pi) + p["actor.logstd"]).sum()   # Normal.entropy summed over A (any row)
     entropy = -ent
@@ -216,3 +238,34 @@ def row_groups(ref):
     zero = ((r > hi) & (a > 0)) | ((r < lo) & (a < 0))
     live = ((r > hi) & (a < 0)) | ((r < lo) & (a > 0))
     return inside, zero, live
+
+
+def check_against_float64(cid, case, which, grads, acc, kl, bound, names=NAMES, losses_too=True):
+    """The GPU suites' conditions on one minibatch: every tensor of `names`
+    within `bound` of the float64 reference under rel_err (printed beside
+    float32 autograd's figure); the policy loss within 1e-6 of mean|min-term|,
+    approx_kl (acc[3] and the kl slot) within 1e-5 of mean|dlogp|, the value
+    and entropy losses within 1e-6 relative.  Returns the errors by name."""
+    ref = reference(case, which)
+    if which not in case._e32:
+        case._e32[which] = fp32_autograd_errors(case, which)
+    e32 = case._e32[which]
+    errs = {}
+    for k in names:
+        assert grads[k].shape == ref["grads"][k].shape and bool(torch.isfinite(grads[k]).all()), (cid, which, k)
+        errs[k] = rel_err(grads[k], ref["grads"][k])
+        print(f"{cid} {which} {k}: e = {errs[k]:.2e} (float32 autograd {e32[k]:.2e})")
+    bad = {k: (v, e32[k]) for k, v in errs.items() if not v <= bound}
+    assert not bad, (cid, which, bad)
+    if not losses_too:
+        return errs
+    pol, val, ent, akl = (float(x) for x in acc)
+    d_pol, d_kl = abs(pol - ref["policy"]), max(abs(float(kl) - ref["approx_kl"]), abs(akl - ref["approx_kl"]))
+    print(f"{cid} {which} losses: policy {d_pol / ref['mean_abs_min_term']:.1e} of mean|min-term|, approx_kl "
+          f"{d_kl / ref['mean_abs_dlogp']:.1e} of mean|dlogp|, value {abs(val / ref['value'] - 1):.1e}, "
+          f"entropy {abs(ent / ref['entropy'] - 1):.1e} relative")
+    assert d_pol <= 1e-6 * ref["mean_abs_min_term"], (pol, ref["policy"])
+    assert d_kl <= 1e-5 * ref["mean_abs_dlogp"], (float(kl), akl, ref["approx_kl"])
+    assert abs(val - ref["value"]) <= 1e-6 * abs(ref["value"]), (val, ref["value"])
+    assert abs(ent - ref["entropy"]) <= 1e-6 * abs(ref["entropy"]), (ent, ref["entropy"])
+    return errs

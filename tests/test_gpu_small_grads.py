@@ -84,25 +84,7 @@ def _run(case, idx, work):
 
 
 def _check_against_float64(cid, case, which, grads, acc, kl):
-    ref = sg.reference(case, which)
-    e32 = sg.fp32_autograd_errors(case, which)
-    errs = {}
-    for k in sg.NAMES:
-        assert grads[k].shape == ref["grads"][k].shape and bool(torch.isfinite(grads[k]).all()), (cid, which, k)
-        errs[k] = sg.rel_err(grads[k], ref["grads"][k])
-        print(f"{cid} {which} {k}: e = {errs[k]:.2e} (float32 autograd {e32[k]:.2e})")
-    pol, val, ent, akl = (float(x) for x in acc)
-    d_pol, d_kl = abs(pol - ref["policy"]), max(abs(float(kl) - ref["approx_kl"]), abs(akl - ref["approx_kl"]))
-    print(f"{cid} {which} losses: policy {d_pol / ref['mean_abs_min_term']:.1e} of mean|min-term|, approx_kl "
-          f"{d_kl / ref['mean_abs_dlogp']:.1e} of mean|dlogp|, value {abs(val / ref['value'] - 1):.1e}, "
-          f"entropy {abs(ent / ref['entropy'] - 1):.1e} relative")
-    bad = {k: (v, e32[k]) for k, v in errs.items() if not v <= GRAD_BOUND}
-    assert not bad, (cid, which, bad)
-    assert d_pol <= 1e-6 * ref["mean_abs_min_term"], (pol, ref["policy"])
-    assert d_kl <= 1e-5 * ref["mean_abs_dlogp"], (float(kl), akl, ref["approx_kl"])
-    assert val == pytest.approx(ref["value"], rel=1e-6)
-    assert ent == pytest.approx(ref["entropy"], rel=1e-6)
-    return errs
+    return sg.check_against_float64(cid, case, which, grads, acc, kl, GRAD_BOUND)
 
 
 @pytest.mark.parametrize("i", range(len(sg.CASES)), ids=sg.CASE_IDS)
