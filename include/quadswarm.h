@@ -822,6 +822,77 @@ int qs_prior_cem_set(qs_cem* p, const qs_prior_spec* spec);
 int qs_prior_cem_buffers(const qs_cem* p, float** prior_actions, float** prior_obs);
 int qs_prior_cem_rollout(qs_cem* p, void* stream);
 
+/* Sampling spec of the MPPI, CEM and particle ticks: time-correlated noise for all
+ * three, and for the CEM tick an elite memory (iCEM, Pinneri et al. 2020).  An
+ * attachable spec like the value tail and the prior; a planner that never had one
+ * launches and writes exactly what it did before, and so does one with the all-zero
+ * spec.  (New entry points of ABI 4, like qs_prior_*.)
+ *
+ *  - Correlated noise.  Let xi_j be the float32 normal that qs_mppi_sample /
+ *    qs_cem_sample / qs_smc_sample form for step j of candidate c > 0, env e, drone
+ *    d, component a (the same Philox key and counter, the same u_k and Box-Muller
+ *    pairs).  With a spec attached the noise of component a is
+ *      eps_0 = xi_0,   eps_j = rho[a] · eps_{j-1} + s_a · xi_j   (j >= 1),
+ *    s_a = (float)sqrt(1 - (double)rho[a]^2) formed once on the host, the two
+ *    products and the sum each rounded to float32 (no multiply-add is contracted).
+ *    A component with rho[a] = 0 takes eps_j = xi_j with no arithmetic: today's
+ *    bytes.  The candidate is formed as before with eps for z: clamp(mean + std ·
+ *    eps_j, lo, hi), the mean copied where the spread is 0, candidate 0 the mean
+ *    itself.  eps has unit variance at every step and corr(eps_j, eps_k) =
+ *    rho^|j - k|.  Where some rho[a], a < A, is not 0 the sample launch is another
+ *    kernel over the same workgroups in x and no y: one thread per (c, e, d) walks
+ *    the steps with eps in registers, one Philox call per step.  The launch count
+ *    of a tick does not change; the prior's inject launch follows it unchanged.
+ *    Per-drone planners take the env-level planner's noise byte for byte, as before.
+ *  - Particle tick.  qs_smc_sample(p, s) runs the recurrence over the steps of
+ *    segment s only: eps = xi at a segment's first step.  Resampling reassigns
+ *    the particles between segments and no noise state follows them through
+ *    parents, so segment = 1 makes rho a no-op.
+ *  - Elite memory (keep > 0, CEM only).  The planner owns kept [n][keep][E][D][A]
+ *    (float32) and kept_n, one int32 device word, both zeroed when the spec is
+ *    attached; qs_cem_reset zeroes kept_n again (stream-ordered).
+ *    qs_cem_refit(p, i) also writes kept[j][r][e][d][a] =
+ *    candidates[j][elites[r][e]][e][d][a] for r < keep (per-drone mode:
+ *    elites[r][e][d], so a kept row is the composite of every drone's own r-th
+ *    elite slice) and *kept_n = keep, in the refit launch itself, which reads
+ *    those values anyway.  qs_cem_sample(p, i) makes candidates 1 .. *kept_n bit
+ *    copies of kept rows 0 .. *kept_n - 1 in the place of drawing them, not
+ *    clipped again, in the sample launch itself (the count is read on the device,
+ *    so the first iteration after create or reset injects nothing, iteration 0 of
+ *    a later tick sees the previous tick's elites, and a captured plan replays
+ *    correctly; the other candidates are the bytes they would be without keep).
+ *    qs_cem_finish shifts kept as it shifts mean: kept[j] = kept[j + 1], the last
+ *    step holds, by more workgroups of the finish launch.  A tick of I iterations
+ *    is begin, I × (sample, score, select, refit), finish as before: keep adds no
+ *    launch.  Slot 0 is the mean, slots 1 .. keep the elite memory, the last `count` slots a policy prior's; they never overlap
+ *    (refusals).  The value tail is independent of all this.  The score launch is
+ *    deterministic and a candidate's outputs do not depend on its slot, so a kept
+ *    elite scores the same bits again: without a value tail iter_best[i + 1][e] >=
+ *    iter_best[i][e] within a tick, for every env.
+ *  - qs_sampling_*_set copy the spec (NULL detaches) and, with keep > 0, allocate
+ *    kept and kept_n; qs_sampling_cem_buffers returns the two pointers, NULL
+ *    without a spec or with keep = 0.  They are host calls that may synchronise
+ *    the device, not stream-ordered: do not capture them.
+ *
+ * Refusals (QS_E_INVALID with a message that names the entry point and the field;
+ * the planner, and a spec attached earlier, are as they were): a null planner;
+ * rho[a] outside [0, 1) or not finite for some a < A; reserved != 0; keep < 0;
+ * keep != 0 on an MPPI or particle planner; keep > elites; 1 + keep + the prior's
+ * count > candidates (also refused by qs_prior_cem_set where the sampling spec is
+ * attached first); a step of kept (keep · E · D · A · 4 bytes) past the 32-bit
+ * offsets.                                                                       */
+typedef struct qs_sampling_spec {
+  float rho[4];              /* per action component (first A used): AR(1)
+                                coefficient in [0, 1)                               */
+  int32_t keep;              /* CEM only: elites carried over, 0 .. min(elites,
+                                candidates - 1 - prior count); 0 for MPPI / SMC     */
+  int32_t reserved;          /* must be 0                                           */
+} qs_sampling_spec;
+
+int qs_sampling_mppi_set(qs_mppi* p, const qs_sampling_spec* spec);
+int qs_sampling_cem_set(qs_cem* p, const qs_sampling_spec* spec);
+int qs_sampling_cem_buffers(const qs_cem* p, float** kept, int32_t** kept_n);
+
 /* Particle (sequential Monte Carlo) planner tick on top of a branch set: fork C
  * particles from the handle's current state, run the horizon in S = ceil(n / L)
  * segments of at most L steps, each "sample actions, advance the particles, weigh
@@ -955,6 +1026,7 @@ int qs_smc_advance(qs_smc* p, int segment, void* stream);
 int qs_smc_resample(qs_smc* p, int segment, void* stream);
 int qs_smc_finish(qs_smc* p, void* stream);
 int qs_smc_plan(qs_smc* p, void* stream);
+int qs_sampling_smc_set(qs_smc* p, const qs_sampling_spec* spec);   /* the sampling spec above, on a particle planner */
 
 /* Multi-step launches this handle has made so far (host, no device work):
  * out[0] on the general multi-step kernel instances, out[1] on the

@@ -4,7 +4,9 @@
 // Three kernels round the one qs_score launch: planner_sample_kernel (shared with
 // the CEM tick, planner_common.h) perturbs the nominal sequence into C candidates
 // (with a policy prior attached, planner_prior.hip, the last of them are then
-// overwritten with the actor's closed-loop rollouts),
+// overwritten with the actor's closed-loop rollouts; with a sampling spec that has a
+// non-zero rho, qs_sampling_mppi_set, planner_sample_ar_kernel takes its place: the
+// same launch count, time-correlated noise),
 // mppi_weights_* turns qs_score's ret / first_done into softmax weights per env,
 // and mppi_sum_* folds the candidates back into the nominal, shifted by one step.
 // Everything per env is summed in double in a fixed order (no atomics), the tick
@@ -215,9 +217,7 @@ int sample_impl(qs_mppi* p, hipStream_t st) {
   P.n = p->n; P.C = p->C; P.E = p->E; P.D = p->D; P.A = p->A;
   for (int a = 0; a < 4; ++a) P.spread.sigma[a] = p->spec.sigma[a];
   P.lo = p->spec.lo; P.hi = p->spec.hi;
-  hipLaunchKernelGGL(qs::planner_sample_kernel<SigmaArg>, dim3(p->grids.sample, (uint32_t)p->n), dim3(qs::kMppiThreads), 0,
-                     st, P);
-  PLANNER_HIP_TRY(hipGetLastError());
+  if (int rc = qs::planner_launch_sample(p, P, p->grids.sample, st)) return rc;   // (serial in j with a correlated sampling spec)
   return qs::prior_inject(p, P.cand, st);   // (nothing without a prior)
 }
 
@@ -329,6 +329,10 @@ int qs_prior_mppi_rollout(qs_mppi* p, void* stream) {
   if (!p) return qs::set_last_error(QS_E_INVALID, "qs_prior_mppi_rollout: null planner");
   if (int rc = qs::planner_ready("qs_prior_mppi_rollout", p)) return rc;
   return prior_impl(p, stream);
+}
+
+int qs_sampling_mppi_set(qs_mppi* p, const qs_sampling_spec* spec) {
+  return qs::sampling_attach("qs_sampling_mppi_set", p, qs::kSamplingMppi, 0, spec);
 }
 
 int qs_mppi_plan(qs_mppi* p, void* stream) {

@@ -3,7 +3,14 @@
 //
 // A tick is begin, I × (sample, qs_score, refit), finish (with a policy prior
 // attached, planner_prior.hip: begin, the prior stage, and every sample followed by
-// the inject launch).  The sample is
+// the inject launch).  With a sampling spec (qs_sampling_cem_set, sampling_sizes.h) a
+// non-zero rho swaps the sample launch for planner_sample_ar_kernel, one launch for
+// one, and keep > 0 adds the elite memory inside the launches there are: the refit
+// kernel also stores the first `keep` elite rows it reads into `kept`, the sample
+// kernel copies them over candidates 1 .. *kept_n in place of drawing those, and the
+// finish kernel's grid grows by kept's columns, which it shifts as it shifts the mean.
+// The launch count of a tick is the same with and without the spec.
+// The sample is
 // planner_sample_kernel (shared with the MPPI tick, planner_common.h) with a
 // per-element spread and the iteration in the Philox counter; cem_select_* ranks
 // an env's candidates by their penalised
@@ -47,6 +54,13 @@ struct RefitParams {
   double alpha;
   int n, C, K, E, A, row, rowp;   // rowp = the power of two >= row
   float sigma[4], sigma_min[4];
+  // The elite memory (a sampling spec with keep > 0; null: none): the refit also
+  // writes kept[j][r][e][row] = cand[j][elites[r][e]][e][row] for r < keep, the values
+  // it reads anyway, and *kept_n = keep.  In per-drone mode e is an agent, so a kept
+  // row is the composite of every drone's own r-th elite slice.
+  float* kept;               // [n][keep][E][row]
+  int32_t* kept_n;           // [1]
+  int keep;
 };
 
 struct FillParams {
@@ -62,6 +76,8 @@ struct FinishParams {
   uint64_t* tick;
   uint64_t col;              // E · D · A
   int n;
+  float* kept;               // [n][keep][E][D][A], or null: the elite memory shifts as the mean does
+  uint64_t kept_col;         // keep · E · D · A
 };
 
 // ---- begin: the spread restarts at sigma ---------------------------------------
@@ -240,8 +256,13 @@ __global__ __launch_bounds__(qs::kCemThreads) void cem_refit_thread_kernel(Refit
   const size_t ek = t % step;
   const int e = (int)(ek / P.row), k = (int)(ek % P.row);
   const float* cj = P.cand + (size_t)j * P.C * step + ek;
+  if (t == 0 && P.kept) *P.kept_n = P.keep;
   double sum = 0.0;
-  for (int r = 0; r < P.K; ++r) sum += (double)cj[(size_t)P.elites[(size_t)r * P.E + e] * step];
+  for (int r = 0; r < P.K; ++r) {
+    const float x = cj[(size_t)P.elites[(size_t)r * P.E + e] * step];
+    if (r < P.keep) P.kept[((size_t)j * P.keep + r) * step + ek] = x;   // (keep = 0 without elite memory)
+    sum += (double)x;
+  }
   const double m = sum / (double)P.K;
   double sq = 0.0;
   for (int r = 0; r < P.K; ++r) {
@@ -272,9 +293,14 @@ __global__ __launch_bounds__(qs::kCemBlockThreads) void cem_refit_block_kernel(R
   const size_t step = (size_t)P.E * P.row;
   const float* cj = P.cand + (size_t)j * P.C * step + (size_t)e * P.row;
   double acc = 0.0;
+  if (blockIdx.x == 0 && tid == 0 && P.kept) *P.kept_n = P.keep;
   if (k < P.row) {
 #pragma unroll 4
-    for (int r = g; r < P.K; r += G) acc += (double)cj[(size_t)sh_el[r] * step + k];
+    for (int r = g; r < P.K; r += G) {
+      const float x = cj[(size_t)sh_el[r] * step + k];
+      if (r < P.keep) P.kept[((size_t)j * P.keep + r) * step + (size_t)e * P.row + k] = x;   // (keep = 0 without elite memory)
+      acc += (double)x;
+    }
   }
   const double m = block_row_sum(acc, part, tid, rowp) / (double)P.K;
   acc = 0.0;
@@ -294,7 +320,12 @@ __global__ __launch_bounds__(qs::kCemBlockThreads) void cem_refit_block_kernel(R
 __global__ __launch_bounds__(qs::kCemThreads) void cem_finish_kernel(FinishParams P) {
   const uint64_t t = (uint64_t)blockIdx.x * qs::kCemThreads + threadIdx.x;
   if (t == 0) *P.tick += 1;
-  if (t >= P.col) return;
+  if (t >= P.col) {   // the threads past the mean's columns walk the elite memory's
+    const uint64_t u = t - P.col;
+    if (!P.kept || u >= P.kept_col) return;
+    for (int j = 0; j + 1 < P.n; ++j) P.kept[(size_t)j * P.kept_col + u] = P.kept[(size_t)(j + 1) * P.kept_col + u];
+    return;
+  }
   float cur = P.mean[t];
   P.action[t] = cur;
   for (int j = 0; j + 1 < P.n; ++j) {
@@ -338,9 +369,12 @@ int sample_impl(qs_cem* p, int iteration, hipStream_t st) {
   P.tag = (uint32_t)qs::kCemTag; P.iter = (uint32_t)iteration;
   P.n = p->n; P.C = p->C; P.E = p->E; P.D = p->D; P.A = p->A;
   P.lo = p->spec.lo; P.hi = p->spec.hi;
-  hipLaunchKernelGGL(qs::planner_sample_kernel<StdMem>, dim3(p->grids.sample, (uint32_t)p->n), dim3(qs::kCemThreads), 0, st,
-                     P);
-  PLANNER_HIP_TRY(hipGetLastError());
+  if (const qs::SamplingState* s = p->sampling; s && s->keep > 0) {   // candidates 1 .. *kept_n: the elite memory
+    P.kept = s->kept;
+    P.kept_n = s->kept_n;
+    P.keep = (uint32_t)s->keep;
+  }
+  if (int rc = qs::planner_launch_sample(p, P, p->grids.sample, st)) return rc;   // (serial in j with a correlated sampling spec)
   return qs::prior_inject(p, P.cand, st);   // (nothing without a prior)
 }
 
@@ -370,6 +404,11 @@ int refit_impl(qs_cem* p, int iteration, hipStream_t st) {
   R.row = p->row();
   R.rowp = qs::mppi_row_pow2(R.row);
   for (int a = 0; a < 4; ++a) { R.sigma[a] = p->spec.sigma[a]; R.sigma_min[a] = p->spec.sigma_min[a]; }
+  const qs::SamplingState* smp = p->sampling;
+  const bool keeps = smp && smp->keep > 0;
+  R.kept = keeps ? smp->kept : nullptr;
+  R.kept_n = keeps ? smp->kept_n : nullptr;
+  R.keep = keeps ? smp->keep : 0;
   if (p->variant == qs::kCemPerBlock) {
     hipLaunchKernelGGL(cem_select_block_kernel, dim3(p->grids.select), dim3(qs::kCemBlockThreads), 0, st, S);
     PLANNER_HIP_TRY(hipGetLastError());
@@ -390,7 +429,13 @@ int finish_impl(qs_cem* p, hipStream_t st) {
   P.tick = (uint64_t*)p->buf[qs::kCemTick];
   P.col = p->bytes[qs::kCemAction] / 4u;
   P.n = p->n;
-  hipLaunchKernelGGL(cem_finish_kernel, dim3(p->grids.finish), dim3(qs::kCemThreads), 0, st, P);
+  const qs::SamplingState* smp = p->sampling;
+  const bool keeps = smp && smp->keep > 0;
+  P.kept = keeps ? smp->kept : nullptr;
+  P.kept_col = keeps ? (uint64_t)smp->keep * P.col : 0;
+  // with elite memory the grid also covers kept's columns: the launch count does not change
+  const uint32_t grid = keeps ? qs::sampling_finish_grid(smp->keep, p->E, p->D, p->A) : p->grids.finish;
+  hipLaunchKernelGGL(cem_finish_kernel, dim3(grid), dim3(qs::kCemThreads), 0, st, P);
   PLANNER_HIP_TRY(hipGetLastError());
   return QS_OK;
 }
@@ -468,7 +513,10 @@ int qs_cem_buffers(const qs_cem* p, qs_cem_bufs* out) {
 
 int qs_cem_reset(qs_cem* p, const float* mean, void* stream) {
   if (!p) return qs::set_last_error(QS_E_INVALID, "qs_cem_reset: null planner");
-  return qs::planner_reset(p, qs::kCemMean, qs::kCemTick, mean, (hipStream_t)stream);
+  if (int rc = qs::planner_reset(p, qs::kCemMean, qs::kCemTick, mean, (hipStream_t)stream)) return rc;
+  if (p->sampling && p->sampling->kept_n)   // the elite memory starts empty again
+    PLANNER_HIP_TRY(hipMemsetAsync(p->sampling->kept_n, 0, 4, (hipStream_t)stream));
+  return QS_OK;
 }
 
 int qs_cem_begin(qs_cem* p, void* stream) {
@@ -515,6 +563,17 @@ int qs_prior_cem_rollout(qs_cem* p, void* stream) {
   if (!p) return qs::set_last_error(QS_E_INVALID, "qs_prior_cem_rollout: null planner");
   if (int rc = qs::planner_ready("qs_prior_cem_rollout", p)) return rc;
   return prior_impl(p, stream);
+}
+
+int qs_sampling_cem_set(qs_cem* p, const qs_sampling_spec* spec) {
+  return qs::sampling_attach("qs_sampling_cem_set", p, qs::kSamplingCem, p ? p->spec.elites : 0, spec);
+}
+
+int qs_sampling_cem_buffers(const qs_cem* p, float** kept, int32_t** kept_n) {
+  if (!p || !kept || !kept_n) return qs::set_last_error(QS_E_INVALID, "qs_sampling_cem_buffers: null argument");
+  *kept = p->sampling ? p->sampling->kept : nullptr;
+  *kept_n = p->sampling ? p->sampling->kept_n : nullptr;
+  return QS_OK;
 }
 
 int qs_cem_plan(qs_cem* p, void* stream) {

@@ -250,6 +250,8 @@ void prior_release(PlannerBase* p) {
   p->prior = nullptr;
 }
 
+int prior_count(const PlannerBase* p) { return p->prior ? p->prior->K : 0; }
+
 int prior_attach(const char* who, PlannerBase* p, const qs_prior_spec* spec) {
   if (!p) return set_last_error(QS_E_INVALID, std::string(who) + ": null planner");
   PLANNER_HIP_TRY(hipSetDevice(p->info.device));
@@ -262,6 +264,11 @@ int prior_attach(const char* who, PlannerBase* p, const qs_prior_spec* spec) {
   if (int rc = qs_get_dims(p->h, &d)) return rc;
   const PriorShape shape{p->n, spec->count, p->C, p->E, p->D, d.obs_dim, p->A};
   if (const PriorRefusal r = prior_refusal(spec_shape(spec, spec->count), shape)) return refuse(who, r, spec, shape);
+  if (p->sampling && !sampling_slots_ok(p->C, p->sampling->keep, spec->count))   // (qs_sampling_cem_set: slots 1 .. keep)
+    return set_last_error(QS_E_INVALID, std::string(who) + ": 1 + the sampling spec's keep + count = 1 + " +
+                                            std::to_string(p->sampling->keep) + " + " + std::to_string(spec->count) +
+                                            " is above candidates = " + std::to_string(p->C) +
+                                            " (the mean, the kept elites and the prior's rollouts each need their own slots)");
   PriorState* v = new (std::nothrow) PriorState;
   if (!v) return set_last_error(QS_E_NOMEM, std::string(who) + ": out of host memory");
   v->spec = *spec;

@@ -3,7 +3,8 @@
 //
 // A tick is begin (fork the planner's branch set), then per segment s of at most L
 // steps: sample (planner_sample_kernel, shared with the MPPI and CEM ticks, over
-// the segment's steps), advance (qs_branch_advance) and resample (smc_weigh_*:
+// the segment's steps; planner_sample_ar_kernel with a correlated sampling spec,
+// qs_sampling_smc_set, its recurrence restarting at the segment), advance (qs_branch_advance) and resample (smc_weigh_*:
 // weights, effective sample size and, where that is low, systematic resampling
 // into parents[s]; then qs_branch_select), then finish: the final weights, the
 // ancestry trace back through parents (smc_trace_kernel) and the weighted sum of
@@ -396,9 +397,9 @@ int sample_impl(qs_smc* p, int s, hipStream_t st) {
   P.n = len; P.C = p->C; P.E = p->E; P.D = p->D; P.A = p->A;
   for (int a = 0; a < 4; ++a) P.spread.sigma[a] = p->spec.sigma[a];
   P.lo = p->spec.lo; P.hi = p->spec.hi;
-  hipLaunchKernelGGL(qs::planner_sample_kernel<SigmaArg>, dim3(p->grids.sample, (uint32_t)len), dim3(qs::kSmcThreads), 0, st, P);
-  PLANNER_HIP_TRY(hipGetLastError());
-  return QS_OK;
+  // with a correlated sampling spec (qs_sampling_smc_set) the recurrence runs over these `len` steps only: it
+  // restarts at every segment, since resampling reassigns the particles in between
+  return qs::planner_launch_sample(p, P, p->grids.sample, st);
 }
 
 int advance_impl(qs_smc* p, int s, void* stream) {
@@ -606,6 +607,10 @@ int qs_smc_resample(qs_smc* p, int segment, void* stream) {
 int qs_smc_finish(qs_smc* p, void* stream) {
   if (!p) return qs::set_last_error(QS_E_INVALID, "qs_smc_finish: null planner");
   return finish_impl(p, (hipStream_t)stream);
+}
+
+int qs_sampling_smc_set(qs_smc* p, const qs_sampling_spec* spec) {
+  return qs::sampling_attach("qs_sampling_smc_set", p, qs::kSamplingSmc, 0, spec);
 }
 
 int qs_smc_plan(qs_smc* p, void* stream) {

@@ -113,6 +113,11 @@ class QsPriorSpec(ctypes.Structure):
                 ("count", ctypes.c_int32), ("obs", ctypes.c_void_p)]
 
 
+class QsSamplingSpec(ctypes.Structure):
+    """include/quadswarm.h qs_sampling_spec: the AR(1) coefficients and the CEM elite memory of a sampling spec."""
+    _fields_ = [("rho", ctypes.c_float * 4), ("keep", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class QsSmcSpec(ctypes.Structure):
     """include/quadswarm.h qs_smc_spec: what a particle (SMC) planner is created from."""
     _fields_ = [("horizon", ctypes.c_int32), ("segment", ctypes.c_int32), ("particles", ctypes.c_int32),
@@ -142,6 +147,7 @@ EXPORTS = ("qs_create", "qs_destroy", "qs_last_error", "qs_abi_version", "qs_get
            "qs_value_cem_buffers", "qs_value_cem_score",
            "qs_prior_act", "qs_prior_mppi_set", "qs_prior_mppi_buffers", "qs_prior_mppi_rollout", "qs_prior_cem_set",
            "qs_prior_cem_buffers", "qs_prior_cem_rollout",
+           "qs_sampling_mppi_set", "qs_sampling_cem_set", "qs_sampling_cem_buffers", "qs_sampling_smc_set",
            "qs_branch_create", "qs_branch_destroy", "qs_branch_buffers", "qs_branch_steps", "qs_branch_fork",
            "qs_branch_advance", "qs_branch_select", "qs_branch_state",
            "qs_smc_create", "qs_smc_destroy", "qs_smc_buffers", "qs_smc_branch", "qs_smc_reset", "qs_smc_begin",
@@ -249,6 +255,10 @@ def load():
             getattr(L, f"qs_prior_{who}_set").argtypes = [vp, ctypes.POINTER(QsPriorSpec)]
             getattr(L, f"qs_prior_{who}_buffers").argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
             getattr(L, f"qs_prior_{who}_rollout").argtypes = [vp, vp]
+    if hasattr(L, "qs_sampling_cem_set"):   # (a QS_DEV_LIB build from before the entry points: A/B runs)
+        for who in ("mppi", "cem", "smc"):
+            getattr(L, f"qs_sampling_{who}_set").argtypes = [vp, ctypes.POINTER(QsSamplingSpec)]
+        L.qs_sampling_cem_buffers.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
     if hasattr(L, "qs_branch_create"):   # (a QS_DEV_LIB build from before the entry points: A/B runs)
         L.qs_branch_create.argtypes = [vp, i32, ctypes.POINTER(vp)]
         L.qs_branch_destroy.argtypes = [vp]
@@ -341,7 +351,7 @@ def load():
     L.qs_rms_normalize.argtypes = [i64, ctypes.c_int32, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp]
     for name in EXPORTS:
         if (name in ("qs_launch_counts", "qs_ring_counts", "qs_score_depth", "qs_score") or name.startswith(("qs_mppi_", "qs_cem_", "qs_pd_", "qs_branch_", "qs_smc_"))
-                or name == "qs_score_agents" or name.startswith(("qs_value_", "qs_prior_"))) and not hasattr(L, name):
+                or name == "qs_score_agents" or name.startswith(("qs_value_", "qs_prior_", "qs_sampling_"))) and not hasattr(L, name):
             continue   # (a QS_DEV_LIB build from before the entry point)
         if name not in ("qs_last_error", "qs_learner_last_error", "qs_rms_last_error", "qs_ppo_small_last_error",
                         "qs_rollout_last_error"):

@@ -960,7 +960,59 @@ class _PolicyPrior:
         L.check(getattr(self.lib, fn)(self._p, self._stream()), fn)
 
 
-class MPPIPlanner(_PolicyPrior, _ValueTail, _Planner):
+class _Sampling:
+    """What `MPPIPlanner`, `CEMPlanner` and `SMCPlanner` add for time-correlated noise and,
+    on a CEM planner, an elite memory (qs_sampling_mppi_set / qs_sampling_cem_set /
+    qs_sampling_smc_set, qs_sampling_cem_buffers; include/quadswarm.h)."""
+
+    kept = kept_n = None   # CEM: the views, while a spec with keep > 0 is attached
+
+    def _sampling_fn(self, name):
+        fn = f"qs_sampling_{self._PREFIX[3:]}_{name}"
+        if not hasattr(self.lib, fn):
+            raise L.QuadSwarmError(f"{L.LIB_PATH} has no {fn}: rebuild the HIP extension")
+        return fn
+
+    def _sampling_set(self, spec):
+        fn = self._sampling_fn("set")
+        with torch.cuda.device(self.swarm.device):
+            L.check(getattr(self.lib, fn)(self._p, None if spec is None else ctypes.byref(spec)), fn)
+        self.kept = self.kept_n = None
+        if self._PREFIX == "qs_cem":
+            sw, fn = self.swarm, self._sampling_fn("buffers")
+            kept, kept_n = ctypes.c_void_p(), ctypes.c_void_p()
+            L.check(getattr(self.lib, fn)(self._p, ctypes.byref(kept), ctypes.byref(kept_n)), fn)
+            if kept.value and kept_n.value:
+                shape = (self.horizon, int(spec.keep), sw.num_envs, sw.num_drones, sw.act_dim)
+                self.kept = torch.as_tensor(_DeviceSpan(kept.value, shape, "<f4"), device=sw.device)
+                self.kept_n = torch.as_tensor(_DeviceSpan(kept_n.value, (1,), "<i4"), device=sw.device)
+
+    def set_sampling(self, rho=0.0, keep=0):
+        """Draw the candidates' noise as an AR(1) sequence along the steps: per action
+        component eps_0 = xi_0, eps_j = rho · eps_{j-1} + sqrt(1 - rho²) · xi_j, xi the
+        normals the planner draws anyway, so eps keeps unit variance and a candidate
+        is a smooth deviation from the nominal / mean.  rho: a number or one per
+        action component, each in [0, 1); a component with rho = 0 is drawn as before,
+        byte for byte.  On an `SMCPlanner` the recurrence restarts at every segment
+        (no noise state follows a particle through resampling), so segment = 1 makes
+        rho a no-op.  keep (CEM only, 0 .. elites): the `keep` best candidates of
+        every refit re-enter the next sample as candidates 1 .. keep, across
+        iterations and, shifted by one step, across ticks; `kept` (n, keep, E, D, A)
+        float32 and `kept_n` (1,) int32 then view the planner's buffers and are None
+        otherwise.  A host call: not to be captured.  A refusal (ValueError /
+        QuadSwarmError) leaves the planner, and an earlier spec, as they were."""
+        spec = L.QsSamplingSpec()
+        for a, r in enumerate(self._per_component(rho, "rho")):
+            spec.rho[a] = r
+        spec.keep = int(keep)
+        self._sampling_set(spec)
+
+    def clear_sampling(self):
+        """Detach the sampling spec: independent noise at every step and no elite memory."""
+        self._sampling_set(None)
+
+
+class MPPIPlanner(_Sampling, _PolicyPrior, _ValueTail, _Planner):
     """The native MPPI tick round `QuadSwarm.score` (qs_mppi_*, include/quadswarm.h).
 
     `sample()` draws `candidates` sequences round `nominal` (candidate 0 is the
@@ -994,7 +1046,11 @@ class MPPIPlanner(_PolicyPrior, _ValueTail, _Planner):
     `count` candidates closed-loop rollouts of the trainer's actor, which
     `plan()` forms before it samples (2 · horizon launches more); `prior()` is
     that stage on its own, `prior_actions` / `prior_obs` its results and
-    `clear_prior()` undoes it (`_PolicyPrior`)."""
+    `clear_prior()` undoes it (`_PolicyPrior`).
+
+    `set_sampling(rho)` makes the noise of every candidate an AR(1) sequence along
+    the steps, in the same number of launches; `clear_sampling()` undoes it
+    (`_Sampling`)."""
 
     _PREFIX = "qs_mppi"
 
@@ -1026,7 +1082,7 @@ class MPPIPlanner(_PolicyPrior, _ValueTail, _Planner):
         self._call("update")
 
 
-class CEMPlanner(_PolicyPrior, _ValueTail, _Planner):
+class CEMPlanner(_Sampling, _PolicyPrior, _ValueTail, _Planner):
     """The native CEM tick round `QuadSwarm.score` (qs_cem_*, include/quadswarm.h).
 
     `begin()` restarts the spread `std` at sigma; `sample(i)` draws `candidates`
@@ -1054,7 +1110,14 @@ class CEMPlanner(_PolicyPrior, _ValueTail, _Planner):
     attached every iteration's scoring is followed by the value tail.
     `set_prior`, `prior()` and `clear_prior()` are `MPPIPlanner`'s too: the prior
     stage runs once per tick, after `begin()`, and every iteration's `sample(i)`
-    ends with the actor's rollouts as its last `count` candidates."""
+    ends with the actor's rollouts as its last `count` candidates.
+
+    `set_sampling(rho, keep)` makes the noise an AR(1) sequence along the steps
+    and, with keep > 0, keeps the `keep` best candidates of every refit in `kept`
+    (n, keep, E, D, A): they re-enter the next sample as candidates 1 .. keep
+    (`kept_n` (1,) int32 says how many: 0 until the first refit after a reset), and
+    `finish()` shifts them by one step with the mean, so a good sequence found once
+    is not lost to resampling.  `clear_sampling()` undoes it (`_Sampling`)."""
 
     _PREFIX = "qs_cem"
 
@@ -1094,7 +1157,7 @@ class CEMPlanner(_PolicyPrior, _ValueTail, _Planner):
         self._call("finish")
 
 
-class SMCPlanner(_Planner):
+class SMCPlanner(_Sampling, _Planner):
     """The native particle (sequential Monte Carlo) tick on a branch set (qs_smc_*,
     include/quadswarm.h).
 
@@ -1120,8 +1183,9 @@ class SMCPlanner(_Planner):
     `ret_agent`, `steps`, `get_state`); the planner owns it.  There is no
     per-drone mode: the drones of an env share a branch's state, and no policy
     prior (`MPPIPlanner.set_prior`): the particles are resampled mid-horizon, which
-    a closed-loop trajectory fixed before the tick cannot follow.  The swarm must
-    outlive the planner."""
+    a closed-loop trajectory fixed before the tick cannot follow.  `set_sampling(rho)`
+    correlates the noise along the steps of each segment (`_Sampling`; the sequence
+    restarts at a segment's first step).  The swarm must outlive the planner."""
 
     _PREFIX = "qs_smc"
 
