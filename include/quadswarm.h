@@ -893,6 +893,77 @@ int qs_sampling_mppi_set(qs_mppi* p, const qs_sampling_spec* spec);
 int qs_sampling_cem_set(qs_cem* p, const qs_sampling_spec* spec);
 int qs_sampling_cem_buffers(const qs_cem* p, float** kept, int32_t** kept_n);
 
+/* Tracking cost: a quadratic cost against a caller-supplied reference, summed inside
+ * the score launch next to ret_agent, and the MPPI / CEM ticks that plan on it.  (New
+ * entry points of ABI 4, like qs_step_seq; every name starts with qs_track_.)
+ *
+ * The cost.  For candidate c, env e, drone d, over steps j = 0 .. jd (jd as in
+ * qs_score_out.ret: the env's first done step in that candidate, or n - 1):
+ *   x[0:12]  the drone's pos, rpy, vel, angular velocity after step j and before any
+ *            auto-reset, each cast to float: the values the step writes to
+ *            obs[..., 0:12] (terminal_obs[..., 0:12] on a done step), on fp64 handles too
+ *   row      clamp(base[e] + j, 0, L - 1); base == NULL means 0
+ *   u        the float32 action the step consumed (actions_out)
+ *   s = 0;  for k in 0..11: dd = (double)x[k] - (double)ref[row][e][d][k];
+ *                           s = s + (double)q[k] * (dd * dd)
+ *   if j == n - 1: s = (double)terminal * s
+ *   for a in 0..A-1: s = s + (double)r[a] * ((double)u[a] * (double)u[a])
+ *   cost_agent[c][e][d] += s
+ * in double, k and a ascending, every product and sum rounded on its own (no fused
+ * multiply-add): a plain float64 loop over the launch's outputs gives the same bytes.
+ *
+ *  - ref and base are the caller's device memory, read at every launch and never
+ *    copied: update them in place (base += 1 to step along the reference, base[done]
+ *    = 0 to restart an env's phase) and the next launch, or the next replay of a
+ *    captured one, sees it.  E is the handle's local env count.
+ *  - qs_track_score is qs_score_agents plus cost_agent ([C][E][D] double): every
+ *    other output is, byte for byte, what qs_score_agents writes; depth, refusals,
+ *    no mutation and capture as there.  cost_agent counts as an output in the overlap
+ *    check.  It refuses a NULL spec or cost_agent.
+ *  - qs_track_fold forms the objective in place on caller-owned buffers, in float64,
+ *    every operation rounded on its own, d ascending, one thread per (c, e):
+ *      ret[c][e]          = scale * ret[c][e] - (sum_d cost_agent[c][e][d]) / D
+ *      ret_agent[c][e][d] = scale * ret_agent[c][e][d] - cost_agent[c][e][d]
+ *    each where the pointer is not NULL (ret first: it reads cost_agent only).
+ *  - qs_track_mppi_set / qs_track_cem_set copy the spec's numbers and pointers (NULL
+ *    detaches) and allocate cost_agent, and ret_agent on an env-level planner.  The
+ *    score stage of plan() is then qs_track_score and the fold with the spec's
+ *    reward_scale, so ret (per-drone mode: ret_agent) holds the objective; update,
+ *    select and refit consume it unchanged, done_penalty still applies through
+ *    first_done.  *_score is that stage on its own; *_buffers returns cost_agent and
+ *    the ret_agent in use (NULL without a spec).  The set calls are host calls that
+ *    may synchronise the device: do not capture them.  A planner without a spec
+ *    launches and writes exactly what it did before.
+ *  - Tracking and the value tail do not compose (a discounted tail, an undiscounted
+ *    cost): the second to be attached is refused.  Branch sets and the particle tick
+ *    have no tracking.
+ *
+ * Refusals (QS_E_INVALID with a message that names the entry point; nothing is
+ * written): a null argument; q[k], r[a] (a < A) or terminal negative or not finite;
+ * reward_scale not finite; L < 1; ref NULL or not 16-byte aligned; L * E * D * 48
+ * bytes at or past 2^31.                                                         */
+typedef struct qs_track_spec {
+  const float* ref;      /* device [L][E][D][12] float32, the caller's; read at every launch, never copied; 16-byte aligned */
+  const int32_t* base;   /* device [E] int32 or NULL: row of step 0 for each env; the caller's, read at every launch */
+  int32_t L;             /* >= 1; L * E * D * 48 must stay below 2^31 (32-bit offsets), refused otherwise */
+  float q[12];           /* finite, >= 0 */
+  float r[4];            /* finite, >= 0 (first A used) */
+  float terminal;        /* finite, >= 0: multiplies the state part of the launch's last step */
+  float reward_scale;    /* finite: the task reward's weight in the folded objective (planners, qs_track_fold) */
+} qs_track_spec;
+
+int qs_track_score(qs_handle* h, int n, int C, const float* const* actions,
+                   const qs_step_out* outs, const qs_score_out* score, double* ret_agent,
+                   const qs_track_spec* spec, double* cost_agent, void* stream);
+int qs_track_fold(int C, int E, int D, double reward_scale, double* ret, double* ret_agent,
+                  const double* cost_agent, void* stream);
+int qs_track_mppi_set(qs_mppi* p, const qs_track_spec* spec);
+int qs_track_mppi_buffers(const qs_mppi* p, double** cost_agent, double** ret_agent);
+int qs_track_mppi_score(qs_mppi* p, void* stream);
+int qs_track_cem_set(qs_cem* p, const qs_track_spec* spec);
+int qs_track_cem_buffers(const qs_cem* p, double** cost_agent, double** ret_agent);
+int qs_track_cem_score(qs_cem* p, void* stream);
+
 /* Particle (sequential Monte Carlo) planner tick on top of a branch set: fork C
  * particles from the handle's current state, run the horizon in S = ceil(n / L)
  * segments of at most L steps, each "sample actions, advance the particles, weigh

@@ -565,6 +565,18 @@ int qs_prior_cem_rollout(qs_cem* p, void* stream) {
   return prior_impl(p, stream);
 }
 
+int qs_track_cem_set(qs_cem* p, const qs_track_spec* spec) { return qs::track_attach("qs_track_cem_set", p, spec); }
+
+int qs_track_cem_buffers(const qs_cem* p, double** cost_agent, double** ret_agent) {
+  return qs::track_buffers("qs_track_cem_buffers", p, cost_agent, ret_agent);
+}
+
+int qs_track_cem_score(qs_cem* p, void* stream) {
+  if (!p) return qs::set_last_error(QS_E_INVALID, "qs_track_cem_score: null planner");
+  if (int rc = qs::planner_ready("qs_track_cem_score", p)) return rc;
+  return qs::planner_score(p, p->buf[qs::kCemRet], p->buf[qs::kCemFirstDone], stream);
+}
+
 int qs_sampling_cem_set(qs_cem* p, const qs_sampling_spec* spec) {
   return qs::sampling_attach("qs_sampling_cem_set", p, qs::kSamplingCem, p ? p->spec.elites : 0, spec);
 }

@@ -217,6 +217,7 @@ __device__ __forceinline__ void block_row_reduce(double acc, double* part, int t
 // ---- host --------------------------------------------------------------------------
 struct ValueState;   // planner_value.hip: the attached value's spec copy and buffers
 struct PriorState;   // planner_prior.hip: the attached policy prior's spec copy, branch set and buffers
+struct TrackState;   // planner_track.hip: the attached tracking spec's copy and buffers
 
 // What a planner holds once a sampling spec is attached (qs_sampling_*_set).
 struct SamplingState {
@@ -246,6 +247,7 @@ struct PlannerBase {
   ValueState* value = nullptr;       // qs_value_mppi_set / qs_value_cem_set; null: the plain score
   PriorState* prior = nullptr;       // qs_prior_mppi_set / qs_prior_cem_set; null: every candidate is sampled
   SamplingState* sampling = nullptr; // qs_sampling_*_set; null: white noise and no elite memory
+  TrackState* track = nullptr;       // qs_track_mppi_set / qs_track_cem_set; null: the task's reward alone
   int units() const { return per_drone ? E * D : E; }      // what the kernels take for envs
   int row() const { return per_drone ? A : D * A; }        // components of a unit's row
   int fd_div() const { return per_drone ? D : 1; }         // units per entry of first_done
@@ -323,6 +325,16 @@ int prior_buffers(const char* who, const PlannerBase* p, float** prior_actions, 
 int prior_rollout(const char* who, PlannerBase* p, uint64_t seed, const uint64_t* tick, float lo, float hi, void* stream);
 int prior_inject(PlannerBase* p, float* candidates, void* stream);
 int prior_count(const PlannerBase* p);   // the attached prior's candidates per env, 0 without one
+
+// The tracking cost (planner_track.hip).  track_attach copies the spec and allocates
+// cost_agent, and ret_agent for an env-level planner (a null spec detaches; refused
+// next to a value tail, as value_attach refuses next to tracking); track_score is the
+// score stage with a spec attached: qs_track_score, then the fold launch.
+void track_release(PlannerBase* p);
+int track_attach(const char* who, PlannerBase* p, const qs_track_spec* spec);
+bool track_attached(const PlannerBase* p);
+int track_buffers(const char* who, const PlannerBase* p, double** cost_agent, double** ret_agent);
+int track_score(PlannerBase* p, void* ret, void* first_done, void* stream);
 
 // The sampling spec (qs_sampling_*_set; the arithmetic is sampling_sizes.h).
 inline void sampling_release(PlannerBase* p) {
@@ -437,6 +449,7 @@ void planner_free(T* p) {
   value_release(p);
   prior_release(p);
   sampling_release(p);
+  track_release(p);
 }
 
 // Allocates and zeroes every buffer of p->bytes (and ret_agent where
@@ -493,8 +506,10 @@ inline int planner_ready(const char* who, PlannerBase* p) {
 }
 
 // Scores the candidates from the handle's current state into ret / first_done
-// (and, in per-drone mode, ret_agent).
+// (and, in per-drone mode, ret_agent); with a tracking spec attached, the folded
+// objective (track_score).
 inline int planner_score(PlannerBase* p, void* ret, void* first_done, void* stream) {
+  if (p->track) return track_score(p, ret, first_done, stream);
   const qs_score_out so{ret, (int32_t*)first_done};
   if (p->per_drone)
     return qs_score_agents(p->h, p->n, p->C, p->steps.data(), nullptr, &so, (double*)p->ret_agent, stream);

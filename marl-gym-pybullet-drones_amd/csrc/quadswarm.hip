@@ -21,6 +21,7 @@
 #include "step_launch.h"
 #include "step_fuse.h"
 #include "step_score.h"
+#include "track_sizes.h"
 #include "step_branch.h"
 #include "step_trunc.h"
 #include "planner_link.h"
@@ -371,7 +372,8 @@ static qs::HotShape hot_shape_of(const qs_handle* h, const qs::ParamsMany<T>& P,
 // actions P.act[0 .. P.nsteps-1], whose rows take LDS of their own (the caller
 // has capped P.nsteps by seq_depth); FUSE = 3: the FUSE = 2 launch over P.E
 // virtual envs (qs_score, P.nsteps within score_depth); FUSE = 4: that launch on a
-// branch set's own blocks (qs_branch_advance).  select_only: no launch.
+// branch set's own blocks (qs_branch_advance); FUSE = 5: the FUSE = 3 launch with a
+// tracking cost (qs_track_score).  select_only: no launch.
 template <class T, int FUSE>
 static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t st, LaunchInfo* info, bool select_only,
                          int* kind = nullptr) {
@@ -405,7 +407,7 @@ static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t
       }
     }
   }
-  if constexpr (FUSE == 2 || FUSE == 3 || FUSE == 4) {
+  if constexpr (FUSE == 2 || FUSE == 3 || FUSE == 4 || FUSE == 5) {
     lds = seq_lds_base(h, lds) + (size_t)P.nsteps * qs::kSeqStepBytes * (size_t)h->dims.act_dim;
     if (lds + kLdsStatic > kLdsBytes) return fail(QS_E_INVALID, "launch: the steps' action rows do not fit in LDS");
   }
@@ -417,7 +419,7 @@ static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t
   else if (s.task == QS_TASK_SPIRAL)
     ok = qs::launch_task<T, QS_TASK_SPIRAL, FUSE>(s.act_type, grid, lds, st, P, s.ctrl_freq, s.pyb_freq, s.physics, &fn,
                                                   select_only);
-  else if constexpr (FUSE == 2 || FUSE == 3 || FUSE == 4)
+  else if constexpr (FUSE == 2 || FUSE == 3 || FUSE == 4 || FUSE == 5)
     return fail(QS_E_INVALID, "launch: no action-sequence instances of the Flock / Meetup / LeaderFollower family");
   else
     ok = qs::launch_task<T, qs::kTaskMarl, FUSE>(s.act_type, grid, lds, st, P, s.ctrl_freq, s.pyb_freq, s.physics, &fn,
@@ -771,10 +773,11 @@ static int score_depth(const qs_handle* h) {
   return qs::score_depth(kSeqLdsMax, kLdsStatic + kLdsGrain, image, plan - hist, h->dims.act_dim);
 }
 
-// `who`: the entry point, qs_score or qs_score_agents; ret_agent: the latter's extra output, or null.
+// `who`: the entry point, qs_score, qs_score_agents or qs_track_score; ret_agent: the latter two's extra
+// output, or null; track / cost_agent: qs_track_score's spec (checked by the caller) and its output, or both null.
 template <class T> static int score_impl(const char* who_c, qs_handle* h, int n, int C, const float* const* actions,
                                          const qs_step_out* outs, const qs_score_out* score, double* ret_agent,
-                                         hipStream_t st) {
+                                         const qs_track_spec* track, double* cost_agent, hipStream_t st) {
   const std::string who = std::string(who_c) + ": ";
   const qs_dims& d = h->dims;
   uint64_t bytes[qs::kScoreOuts], act_bytes = 0;
@@ -811,24 +814,51 @@ template <class T> static int score_impl(const char* who_c, qs_handle* h, int n,
       return fail(QS_E_INVALID, who + "ret_agent of C * num_envs * num_drones doubles is too large (32-bit offsets)");
     room = ranges.add(ret_agent, ab, false) && room;
   }
+  if (cost_agent) {
+    any_out = true;
+    const uint64_t cb = qs::track_cost_bytes(C, d.num_envs, d.num_drones);
+    if (!qs::score_fits(cb))
+      return fail(QS_E_INVALID, who + "cost_agent of C * num_envs * num_drones doubles is too large (32-bit offsets)");
+    // (held against every range by hand: ScoreRanges has room for qs_score_agents' ranges only)
+    const uintptr_t lo = (uintptr_t)cost_agent, hi = lo + (uintptr_t)cb;
+    for (int i = 0; i < ranges.n; ++i)
+      if (lo < ranges.r[i].hi && ranges.r[i].lo < hi)
+        return fail(QS_E_INVALID, who + "cost_agent overlaps another output or an action buffer");
+  }
   if (!any_out) return fail(QS_E_INVALID, who + "nothing to write (no output in outs[] and neither ret nor first_done)");
   if (!room || ranges.overlap())
     return fail(QS_E_INVALID, who + "an output overlaps another output or an action buffer");
+  auto fill = [&](qs::ParamsScore<T>& P) {
+    fill_params(h, P);
+    P.mode = qs::MODE_STEP;
+    P.E_src = d.num_envs;
+    P.E = C * d.num_envs;          // the virtual envs; P.N stays the handle's agent count
+    P.reset_queue = nullptr;       // (score_refusal: none)
+    P.store_state = 0;             // nothing is stored to the handle, ever
+    P.nsteps = n;
+    for (int j = 0; j < n; ++j) {
+      if (outs) P.io[j] = to_io<T>(outs[j]);
+      P.act[j] = actions[j];
+    }
+    if (score) { P.ret = (double*)score->ret; P.first_done = score->first_done; }
+    P.ret_agent = ret_agent;
+  };
+  if (track) {   // the FUSE = 5 instance: the same launch plus the cost
+    qs::ParamsTrack<T> P;
+    std::memset(&P, 0, sizeof(P));
+    fill(P);
+    P.ref = track->ref;
+    P.base = track->base;
+    P.L = track->L;
+    for (int k = 0; k < qs::kTrackState; ++k) P.q[k] = track->q[k];
+    for (int k = 0; k < qs::kTrackMaxAct; ++k) P.r[k] = k < d.act_dim ? track->r[k] : 0.0f;
+    P.terminal = track->terminal;
+    P.cost_agent = cost_agent;
+    return launch_kernel<T, 5>(h, P, st, nullptr, false);
+  }
   qs::ParamsScore<T> P;
   std::memset(&P, 0, sizeof(P));
-  fill_params(h, P);
-  P.mode = qs::MODE_STEP;
-  P.E_src = d.num_envs;
-  P.E = C * d.num_envs;          // the virtual envs; P.N stays the handle's agent count
-  P.reset_queue = nullptr;       // (score_refusal: none)
-  P.store_state = 0;             // nothing is stored to the handle, ever
-  P.nsteps = n;
-  for (int j = 0; j < n; ++j) {
-    if (outs) P.io[j] = to_io<T>(outs[j]);
-    P.act[j] = actions[j];
-  }
-  if (score) { P.ret = (double*)score->ret; P.first_done = score->first_done; }
-  P.ret_agent = ret_agent;
+  fill(P);
   return launch_kernel<T, 3>(h, P, st, nullptr, false);
 }
 
@@ -1233,11 +1263,39 @@ int qs_step_seq(qs_handle* h, int n, const float* const* actions, const qs_step_
 
 int qs_score_depth(const qs_handle* h) { return h ? score_depth(h) : 0; }
 
-// qs_score and qs_score_agents (ret_agent null: the same call under the other name).
+// Why a tracking spec is refused against handle h (track_sizes.h), as the message after the entry point's name.
+static const char* track_refusal_text(const qs_handle* h, const qs_track_spec* s) {
+  qs::TrackSpecShape v;
+  v.ref = (uintptr_t)s->ref;
+  v.L = s->L;
+  for (int k = 0; k < qs::kTrackState; ++k) v.q[k] = s->q[k];
+  for (int k = 0; k < qs::kTrackMaxAct; ++k) v.r[k] = s->r[k];
+  v.terminal = s->terminal;
+  v.reward_scale = s->reward_scale;
+  switch (qs::track_refusal(v, h->dims.num_envs, h->dims.num_drones, h->dims.act_dim)) {
+    case qs::kTrackRefNull: return "ref is null";
+    case qs::kTrackRefAlign: return "ref must be 16-byte aligned";
+    case qs::kTrackRows: return "L must be >= 1";
+    case qs::kTrackQ: return "q[0 .. 11] must be finite and >= 0";
+    case qs::kTrackR: return "r[a] must be finite and >= 0 for each action component";
+    case qs::kTrackTerminal: return "terminal must be finite and >= 0";
+    case qs::kTrackScale: return "reward_scale must be finite";
+    case qs::kTrackOffsets: return "L * num_envs * num_drones * 48 bytes of ref are past the 32-bit offsets";
+    default: return nullptr;
+  }
+}
+
+// qs_score, qs_score_agents (ret_agent null: the same call under the other name) and qs_track_score
+// (tracking: spec and cost_agent must be there).
 static int score_entry(const char* who_c, qs_handle* h, int n, int C, const float* const* actions, const qs_step_out* outs,
-                       const qs_score_out* score, double* ret_agent, void* stream) {
+                       const qs_score_out* score, double* ret_agent, void* stream, bool tracking = false,
+                       const qs_track_spec* track = nullptr, double* cost_agent = nullptr) {
   const std::string who = std::string(who_c) + ": ";
   if (!h) return fail(QS_E_INVALID, who + "null handle");
+  if (tracking) {
+    if (!track) return fail(QS_E_INVALID, who + "spec is null");
+    if (!cost_agent) return fail(QS_E_INVALID, who + "cost_agent is null");
+  }
   if (const char* why = score_refusal(h)) return fail(QS_E_INVALID, who + "this handle cannot score: " + why);
   const int depth = score_depth(h);
   if (depth < 1) return fail(QS_E_INVALID, who + "this handle cannot score: no step's action rows fit in LDS");
@@ -1248,11 +1306,19 @@ static int score_entry(const char* who_c, qs_handle* h, int n, int C, const floa
   if (!actions) return fail(QS_E_INVALID, who + "actions is null");
   for (int j = 0; j < n; ++j)
     if (!actions[j]) return fail(QS_E_INVALID, who + "actions[" + std::to_string(j) + "] is null");
+  if (tracking)
+    if (const char* why = track_refusal_text(h, track)) return fail(QS_E_INVALID, who + why);
   if (!h->reset_done) return fail(QS_E_STATE, who + "call qs_reset first");
   h->fuse.forget();
   hipStream_t st = (hipStream_t)stream;
-  if (h->dims.precision == 8) return score_impl<double>(who_c, h, n, C, actions, outs, score, ret_agent, st);
-  return score_impl<float>(who_c, h, n, C, actions, outs, score, ret_agent, st);
+  if (h->dims.precision == 8) return score_impl<double>(who_c, h, n, C, actions, outs, score, ret_agent, track, cost_agent, st);
+  return score_impl<float>(who_c, h, n, C, actions, outs, score, ret_agent, track, cost_agent, st);
+}
+
+int qs_track_score(qs_handle* h, int n, int C, const float* const* actions, const qs_step_out* outs,
+                   const qs_score_out* score, double* ret_agent, const qs_track_spec* spec, double* cost_agent,
+                   void* stream) {
+  return score_entry("qs_track_score", h, n, C, actions, outs, score, ret_agent, stream, true, spec, cost_agent);
 }
 
 int qs_score(qs_handle* h, int n, int C, const float* const* actions, const qs_step_out* outs, const qs_score_out* score,

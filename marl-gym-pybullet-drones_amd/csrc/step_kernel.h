@@ -339,9 +339,23 @@ template <class T> struct ParamsRing : ParamsMany<T> {
 template <class T> struct ParamsBranch : ParamsScore<T> {
   int t0;
 };
+// Arguments of the tracking instances (step_kernel FUSE = 5, qs_track_score): the
+// FUSE = 3 launch that also sums each drone's quadratic cost against a reference
+// (track_sizes.h).  ref and base are the caller's, indexed by the handle's env
+// (v mod E_src); the weights are launch constants.  A type of its own again:
+// ParamsScore and ParamsBranch keep their size, and the FUSE = 3 / 4 instances
+// their argument blocks and their code.
+template <class T> struct ParamsTrack : ParamsScore<T> {
+  const float* ref;      // [L][E_src][D][12]
+  const int32_t* base;   // [E_src] or NULL (= 0): the row of step 0
+  int L;
+  float q[12], r[4], terminal;
+  double* cost_agent;    // [E][D]: each drone's cost up to the env's first done step
+};
 template <class T, int FUSE>
-using KernelParams = std::conditional_t<FUSE == 4, ParamsBranch<T>, std::conditional_t<FUSE == 3, ParamsScore<T>,
-    std::conditional_t<FUSE == 2, ParamsSeq<T>, std::conditional_t<FUSE != 0, ParamsMany<T>, Params<T>>>>>;
+using KernelParams = std::conditional_t<FUSE == 5, ParamsTrack<T>, std::conditional_t<FUSE == 4, ParamsBranch<T>,
+    std::conditional_t<FUSE == 3, ParamsScore<T>,
+    std::conditional_t<FUSE == 2, ParamsSeq<T>, std::conditional_t<FUSE != 0, ParamsMany<T>, Params<T>>>>>>;
 
 // ---------------------------------------------------- conversions (external)
 // pybullet getMatrixFromQuaternion = btMatrix3x3::setRotation (s = 2/|q|²).
@@ -878,6 +892,14 @@ template <class T> __device__ __forceinline__ int launch_src_envs(const ParamsSc
 // image with a run-time control frequency) and the env records as the FUSE = 2
 // instances do, and loads and stores the three accumulators.  Still no episode
 // log, no error flag and no store to the handle.
+// FUSE = 5: the FUSE = 3 launch with a tracking cost (qs_track_score, ParamsTrack).
+// Every lane also keeps a second double accumulator under the same `score_live`:
+// the weighted squared distance of its twelve kinematic obs entries (as the floats
+// the obs row holds) from its row of a caller-supplied reference, plus the weighted
+// squared action.  A step's reference row (48 bytes a lane) is loaded at the top of
+// the step, before the PID, and read at the reward stage: the substeps hide it.
+// The weights are launch constants held in SGPRs.  Every other statement is the
+// FUSE = 3 instance's, so the other outputs are its bytes.
 // HOT = 1 (FUSE = 1, MultiHover, compile-time control frequency, AUXM 0 only):
 // the launch shape qs::hot_shape_ok (step_fuse.h) accepts, with everything that
 // predicate fixes for the launch folded in ("hot shape"): D = 8
@@ -974,8 +996,10 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
   // a, stores the state, the history ring and the env record back after the loop,
   // and carries the score from launch to launch (ParamsBranch).  Only the reset
   // draws still go by the source env, v mod E_src.
+  // FUSE = 5 (qs_track_score): the FUSE = 3 launch plus the tracking cost.
   constexpr bool kBranch = FUSE == 4;
-  constexpr bool kScore = FUSE == 3 || kBranch;
+  constexpr bool kTrack = FUSE == 5;
+  constexpr bool kScore = FUSE == 3 || kTrack || kBranch;
   const int e_h = (kScore && !kBranch) ? e % launch_src_envs(P) : e, a_h = (kScore && !kBranch) ? e_h * D + d : a;
   const uint32_t genv = (uint32_t)(P.env_offset + (kBranch ? e % launch_src_envs(P) : e_h));
   // kBlock == 64 is one wave: an env of 2, 4, 8 or 16 drones lies inside one
@@ -1030,6 +1054,11 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
     acc_agent0 = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rsrc(P.ret_agent, (unsigned)N * 8u),
                                                                                valid ? (int)((unsigned)a * 8u) : (int)kOOB, 0, 0));
   }
+  // FUSE = 5: the env's row base (a null buffer reads 0)
+  [[maybe_unused]] int32_t track_base = 0;
+  if constexpr (kTrack)
+    track_base = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc(P.base, P.base ? E * 4u : 0u),
+                                                                valid ? (int)(e_h * 4u) : (int)kOOB, 0, 0);
   issue_fence();
   T pos[3], q[4], vel[3], w[3], lrpm[4], pid[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tgt[3] = {0, 0, 0};
 #pragma unroll
@@ -1080,7 +1109,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
   extern __shared__ float4 dyn_lds4[];   // float4: 16-B aligned staging for the obs stores
   // FUSE = 2: the launch's action rows come first, nsteps · A · kBlock floats
   // (a multiple of 256 bytes: the stage keeps its alignment)
-  constexpr bool kSeq = FUSE == 2 || FUSE == 3 || FUSE == 4;
+  constexpr bool kSeq = FUSE == 2 || FUSE == 3 || FUSE == 4 || FUSE == 5;
   float* const dyn_lds = reinterpret_cast<float*>(dyn_lds4);
   float* const act_lds = dyn_lds;
   float* const hist_pref = kSeq ? dyn_lds + (size_t)launch_steps(P) * kBlock * A : dyn_lds;
@@ -1172,6 +1201,26 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
     score_fd = score_live ? -1 : acc_fd0;
   }
 
+  // FUSE = 5 (every lane): this drone's tracking cost, summed like score_agent; the
+  // reference (L · E · D · 48 bytes < 2^31, track_sizes.h), this lane's drone inside a
+  // row and the weights, all read once
+  [[maybe_unused]] double track_cost = 0;
+  [[maybe_unused]] const float* track_ptr = nullptr;
+  [[maybe_unused]] unsigned track_lane = 0, track_stride = 0;
+  [[maybe_unused]] int track_L = 1, track_last = 0;
+  [[maybe_unused]] float track_q[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, track_w[4] = {0, 0, 0, 0}, track_term = 0;
+  if constexpr (kTrack) {
+    track_L = keep_sgpr(P.L);
+    track_last = keep_sgpr(P.nsteps) - 1;
+    track_stride = keep_sgpr((unsigned)P.E_src * (unsigned)D);              // drones of a reference row
+    track_ptr = keep_sgpr(P.ref);
+    track_lane = valid ? (unsigned)a_h : (unsigned)((blockIdx.x * P.EPB) % P.E_src) * (unsigned)D;   // idle lanes: a row that exists
+#pragma unroll
+    for (int k = 0; k < 12; ++k) track_q[k] = keep_sgpr(P.q[k]);
+#pragma unroll
+    for (int k = 0; k < A; ++k) track_w[k] = keep_sgpr(P.r[k]);
+    track_term = keep_sgpr(P.terminal);
+  }
   float cur_act[A];            // this step's action (newest history entry)
 #pragma unroll
   for (int k = 0; k < A; ++k) cur_act[k] = 0.f;
@@ -1278,6 +1327,28 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
       const uint32_t rr[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
       for (int k = 0; k < A; ++k) cur_act[k] = 2.0f * u01<float>(rr[k]) - 1.0f;
+    }
+  }
+  // FUSE = 5: this step's reference row, clamp(base + ks, 0, L − 1) (no sum that could
+  // wrap: a base at or past L never has ks added), as three 16-byte global loads: the
+  // spec asks for a 16-byte aligned reference and a drone's row is 48 bytes.  (Through
+  // the buffer builtins the wide loads came out as single dwords in this kernel, as the
+  // note at the history loads says of b128, and twelve dword loads stayed twelve.)
+  // Idle lanes read their workgroup's first row, which exists: nothing out of range,
+  // and nothing uses what they read.  The loads land under the PID and the substeps
+  // and are read at the reward stage.
+  [[maybe_unused]] float track_ref[12];
+  if constexpr (kTrack) {
+    int row = track_base >= track_L ? track_L - 1 : track_base + ks;
+    row = row < 0 ? 0 : (row > track_L - 1 ? track_L - 1 : row);
+    // (the pointer went through an SGPR pin, which drops its address space: named again, the loads are global, not flat)
+    typedef float v4f_t __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) v4f_t* g_v4f_ptr_t;
+    const g_v4f_ptr_t r4 = (g_v4f_ptr_t)(reinterpret_cast<const v4f_t*>(track_ptr) + ((size_t)row * track_stride + track_lane) * 3u);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const v4f_t t4 = r4[k];
+      track_ref[4 * k] = t4.x; track_ref[4 * k + 1] = t4.y; track_ref[4 * k + 2] = t4.z; track_ref[4 * k + 3] = t4.w;
     }
   }
   QS_STAMP(1);
@@ -1883,8 +1954,25 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
       done_env = valid && s.done[lenv];
     }
     if constexpr (kScore) {   // the drone's term of this step's reward, up to and including the env's first done step
+      // FUSE = 5: the step's cost of this drone, in double, every product and sum
+      // rounded on its own, from the floats the obs row holds (write_obs_row)
+      [[maybe_unused]] double track_s = 0;
+      if constexpr (kTrack) {
+        const float x[12] = {(float)pos[0], (float)pos[1], (float)pos[2], (float)rpy[0], (float)rpy[1], (float)rpy[2],
+                             (float)vel[0], (float)vel[1], (float)vel[2], (float)angv[0], (float)angv[1], (float)angv[2]};
+#pragma unroll
+        for (int k = 0; k < 12; ++k) {
+          const double dd = __dsub_rn((double)x[k], (double)track_ref[k]);
+          track_s = __dadd_rn(track_s, __dmul_rn((double)track_q[k], __dmul_rn(dd, dd)));
+        }
+        if (ks == track_last) track_s = __dmul_rn((double)track_term, track_s);
+#pragma unroll
+        for (int k = 0; k < A; ++k)
+          track_s = __dadd_rn(track_s, __dmul_rn((double)track_w[k], __dmul_rn((double)cur_act[k], (double)cur_act[k])));
+      }
       if (score_live) {
         score_agent += (double)rterm;
+        if constexpr (kTrack) track_cost = __dadd_rn(track_cost, track_s);
         score_live = !done_env;
       }
     }
@@ -2240,6 +2328,9 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
       if (P.first_done) P.first_done[e] = score_fd < 0 ? (kBranch ? score_t0 : 0) + launch_steps(P) : score_fd;
     }
     if (valid && P.ret_agent) P.ret_agent[a] = score_agent;   // a < C · E · D < 2^31 (step_score.h)
+    if constexpr (kTrack) {
+      if (valid) P.cost_agent[a] = track_cost;
+    }
   }
   // ---------------- per-env records: staged in LDS, stored as one span
   if constexpr (!kScore || kBranch) {

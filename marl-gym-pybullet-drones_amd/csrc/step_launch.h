@@ -10,7 +10,8 @@ namespace qs {
 // P.io[]), in translation units of their own; FUSE = 2: those that read the
 // steps' actions from ParamsSeq::act[], in further ones; FUSE = 3: the branch
 // rollouts of qs_score (ParamsScore), in theirs; FUSE = 4: those of a branch set
-// (qs_branch_advance, ParamsBranch), in theirs.  `fn`, if given, receives the kernel's
+// (qs_branch_advance, ParamsBranch), in theirs; FUSE = 5: the branch rollouts with a
+// tracking cost (qs_track_score, ParamsTrack), in theirs.  `fn`, if given, receives the kernel's
 // function pointer (what a graph kernel node names); `select_only` looks the
 // kernel up without launching it.
 template <class T, int TASK, int FUSE = 0>

@@ -1,7 +1,8 @@
 // step_launch_impl.h — kernel launch dispatch, included by the per-task-family
 // translation units (step_mh.hip, step_spiral.hip, step_marl.hip and their
 // *_fused.hip twins, step_mh_seq.hip, step_spiral_seq.hip, step_mh_score.hip,
-// step_spiral_score.hip, step_mh_branch.hip and step_spiral_branch.hip) so the
+// step_spiral_score.hip, step_mh_branch.hip, step_spiral_branch.hip, step_mh_track.hip
+// and step_spiral_track.hip) so the
 // kernel instantiations compile in parallel.
 #pragma once
 #include "step_launch.h"
@@ -67,3 +68,4 @@ bool launch_task(int act, int grid, size_t lds, hipStream_t st, const KernelPara
 #define QS_INSTANTIATE_LAUNCH_SEQ(TASK) QS_INSTANTIATE_LAUNCH_AS(TASK, 2)
 #define QS_INSTANTIATE_LAUNCH_SCORE(TASK) QS_INSTANTIATE_LAUNCH_AS(TASK, 3)
 #define QS_INSTANTIATE_LAUNCH_BRANCH(TASK) QS_INSTANTIATE_LAUNCH_AS(TASK, 4)
+#define QS_INSTANTIATE_LAUNCH_TRACK(TASK) QS_INSTANTIATE_LAUNCH_AS(TASK, 5)

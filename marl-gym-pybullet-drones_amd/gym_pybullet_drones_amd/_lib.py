@@ -118,6 +118,12 @@ class QsSamplingSpec(ctypes.Structure):
     _fields_ = [("rho", ctypes.c_float * 4), ("keep", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class QsTrackSpec(ctypes.Structure):
+    """include/quadswarm.h qs_track_spec: the reference, row base and weights of a tracking cost."""
+    _fields_ = [("ref", ctypes.c_void_p), ("base", ctypes.c_void_p), ("L", ctypes.c_int32), ("q", ctypes.c_float * 12),
+                ("r", ctypes.c_float * 4), ("terminal", ctypes.c_float), ("reward_scale", ctypes.c_float)]
+
+
 class QsSmcSpec(ctypes.Structure):
     """include/quadswarm.h qs_smc_spec: what a particle (SMC) planner is created from."""
     _fields_ = [("horizon", ctypes.c_int32), ("segment", ctypes.c_int32), ("particles", ctypes.c_int32),
@@ -148,6 +154,8 @@ EXPORTS = ("qs_create", "qs_destroy", "qs_last_error", "qs_abi_version", "qs_get
            "qs_prior_act", "qs_prior_mppi_set", "qs_prior_mppi_buffers", "qs_prior_mppi_rollout", "qs_prior_cem_set",
            "qs_prior_cem_buffers", "qs_prior_cem_rollout",
            "qs_sampling_mppi_set", "qs_sampling_cem_set", "qs_sampling_cem_buffers", "qs_sampling_smc_set",
+           "qs_track_score", "qs_track_fold", "qs_track_mppi_set", "qs_track_mppi_buffers", "qs_track_mppi_score",
+           "qs_track_cem_set", "qs_track_cem_buffers", "qs_track_cem_score",
            "qs_branch_create", "qs_branch_destroy", "qs_branch_buffers", "qs_branch_steps", "qs_branch_fork",
            "qs_branch_advance", "qs_branch_select", "qs_branch_state",
            "qs_smc_create", "qs_smc_destroy", "qs_smc_buffers", "qs_smc_branch", "qs_smc_reset", "qs_smc_begin",
@@ -259,6 +267,14 @@ def load():
         for who in ("mppi", "cem", "smc"):
             getattr(L, f"qs_sampling_{who}_set").argtypes = [vp, ctypes.POINTER(QsSamplingSpec)]
         L.qs_sampling_cem_buffers.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    if hasattr(L, "qs_track_score"):   # (a QS_DEV_LIB build from before the entry points: A/B runs)
+        L.qs_track_score.argtypes = [vp, i32, i32, ctypes.POINTER(vp), ctypes.POINTER(QsStepOut), ctypes.POINTER(QsScoreOut),
+                                     vp, ctypes.POINTER(QsTrackSpec), vp, vp]
+        L.qs_track_fold.argtypes = [i32, i32, i32, ctypes.c_double, vp, vp, vp, vp]
+        for who in ("mppi", "cem"):
+            getattr(L, f"qs_track_{who}_set").argtypes = [vp, ctypes.POINTER(QsTrackSpec)]
+            getattr(L, f"qs_track_{who}_buffers").argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
+            getattr(L, f"qs_track_{who}_score").argtypes = [vp, vp]
     if hasattr(L, "qs_branch_create"):   # (a QS_DEV_LIB build from before the entry points: A/B runs)
         L.qs_branch_create.argtypes = [vp, i32, ctypes.POINTER(vp)]
         L.qs_branch_destroy.argtypes = [vp]
@@ -351,7 +367,7 @@ def load():
     L.qs_rms_normalize.argtypes = [i64, ctypes.c_int32, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp]
     for name in EXPORTS:
         if (name in ("qs_launch_counts", "qs_ring_counts", "qs_score_depth", "qs_score") or name.startswith(("qs_mppi_", "qs_cem_", "qs_pd_", "qs_branch_", "qs_smc_"))
-                or name == "qs_score_agents" or name.startswith(("qs_value_", "qs_prior_", "qs_sampling_"))) and not hasattr(L, name):
+                or name == "qs_score_agents" or name.startswith(("qs_value_", "qs_prior_", "qs_sampling_", "qs_track_"))) and not hasattr(L, name):
             continue   # (a QS_DEV_LIB build from before the entry point)
         if name not in ("qs_last_error", "qs_learner_last_error", "qs_rms_last_error", "qs_ppo_small_last_error",
                         "qs_rollout_last_error"):

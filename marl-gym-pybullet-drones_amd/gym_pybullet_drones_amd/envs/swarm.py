@@ -275,7 +275,7 @@ class QuadSwarm:
 
     _SCORE_OUTS = ("obs", "reward", "terminated", "truncated", "terminal_obs", "reasons", "actions_out")
 
-    def score(self, actions, outs=None, *, ret=None, first_done=None, ret_agent=None):
+    def score(self, actions, outs=None, *, ret=None, first_done=None, ret_agent=None, track=None, cost_agent=None):
         """Run C candidate action sequences of n steps each from the swarm's current
         state in one launch, and leave the swarm exactly as it was (qs_score): no
         state, history, episode log or counter changes.  Virtual env (c, e) starts
@@ -292,7 +292,12 @@ class QuadSwarm:
         or n.  ret_agent: (C, E, D) float64, each drone's own terms of those rewards
         before the division by D, summed over the same steps (qs_score_agents): ret
         is about ret_agent.sum(-1) / D.  At least one output must be named, none may
-        overlap another or an action tensor, and 1 <= n <= score_depth()."""
+        overlap another or an action tensor, and 1 <= n <= score_depth().
+
+        track, cost_agent: a `track_spec(...)` result and a (C, E, D) float64 tensor
+        (both or neither): the same launch also sums each drone's tracking cost
+        against the spec's reference over the same steps (qs_track_score); every
+        other output is the bytes it is without."""
         E, D, A, O = self.num_envs, self.num_drones, self.act_dim, self.obs_dim
         if isinstance(actions, torch.Tensor):
             if actions.dim() != 5:
@@ -311,7 +316,8 @@ class QuadSwarm:
         want = dict(obs=(torch.float32, C * E * D * O), reward=(self.rdtype, C * E), terminated=(torch.uint8, C * E),
                     truncated=(torch.uint8, C * E), terminal_obs=(torch.float32, C * E * D * O),
                     reasons=(torch.uint8, C * E * D), actions_out=(torch.float32, C * E * D * A),
-                    ret=(torch.float64, C * E), first_done=(torch.int32, C * E), ret_agent=(torch.float64, C * E * D))
+                    ret=(torch.float64, C * E), first_done=(torch.int32, C * E), ret_agent=(torch.float64, C * E * D),
+                    cost_agent=(torch.float64, C * E * D))
 
         def buf(t, what):
             if t is None:
@@ -337,6 +343,15 @@ class QuadSwarm:
         if ret is not None or first_done is not None:
             so = ctypes.byref(L.QsScoreOut(buf(ret, "ret"), buf(first_done, "first_done")))
         ptrs = (ctypes.c_void_p * n)(*[a.data_ptr() for a in acts])
+        if (track is None) != (cost_agent is None):
+            raise ValueError("track and cost_agent go together")
+        if track is not None:
+            if not hasattr(self.lib, "qs_track_score"):
+                raise L.QuadSwarmError(f"{L.LIB_PATH} has no qs_track_score: rebuild the HIP extension")
+            spec = _check_track(self, track)
+            L.check(self.lib.qs_track_score(self._h, n, C, ptrs, arr, so, buf(ret_agent, "ret_agent"), ctypes.byref(spec),
+                                            buf(cost_agent, "cost_agent"), self._stream()), "qs_track_score")
+            return
         if ret_agent is None:
             L.check(self.lib.qs_score(self._h, n, C, ptrs, arr, so, self._stream()), "qs_score")
             return
@@ -832,6 +847,107 @@ class _ValueTail:
         L.check(getattr(self.lib, fn)(self._p, self._stream()), fn)
 
 
+def track_spec(ref, q, r=0.0, terminal=1.0, reward_scale=1.0, base=None):
+    """The `QsTrackSpec` of a tracking cost (include/quadswarm.h qs_track_spec) and the
+    tensors it points into, which the caller keeps alive as long as the spec is used.
+
+    ref: (L, E, D, 12) float32 on the GPU, contiguous and 16-byte aligned: the reference
+    of every drone's pos, rpy, vel and angular velocity, row by row.  base: None (every
+    env reads row j at step j) or an (E,) int32 tensor on the same device, the row of
+    step 0 for each env; step j reads row clamp(base + j, 0, L - 1).  Nothing is copied:
+    `ref.copy_(...)`, `base.add_(1)` and `base[done] = 0` are seen by the next launch,
+    also by the next replay of a captured one.  q: twelve state weights (or one number
+    for all), r: the action weights (a number or up to four), terminal: the factor on
+    the state part of the last step, reward_scale: the task reward's weight in the
+    folded objective.  All finite; q, r and terminal >= 0 (the library refuses others)."""
+    if (not isinstance(ref, torch.Tensor) or ref.dtype != torch.float32 or ref.dim() != 4 or ref.shape[-1] != 12
+            or not ref.is_contiguous() or not ref.is_cuda or ref.shape[0] < 1):
+        raise ValueError("ref must be a contiguous float32 (L, E, D, 12) tensor on the GPU")
+    if ref.data_ptr() % 16 != 0:
+        raise ValueError("ref must be 16-byte aligned")
+    spec, keep = L.QsTrackSpec(), [ref]
+    spec.ref, spec.L = ref.data_ptr(), int(ref.shape[0])
+    if base is not None:
+        if (not isinstance(base, torch.Tensor) or base.dtype != torch.int32 or not base.is_contiguous()
+                or base.device != ref.device or tuple(base.shape) != (ref.shape[1],)):
+            raise ValueError(f"base must be a contiguous int32 ({ref.shape[1]},) tensor on {ref.device}")
+        spec.base = base.data_ptr()
+        keep.append(base)
+    qs = [float(q)] * 12 if np.isscalar(q) else [float(v) for v in q]
+    if len(qs) != 12:
+        raise ValueError("q must be a number or twelve (pos, rpy, vel, angular velocity)")
+    rs = [float(r)] * 4 if np.isscalar(r) else [float(v) for v in r]
+    if len(rs) > 4:
+        raise ValueError("r must be a number or at most four (one per action component)")
+    rs += [0.0] * (4 - len(rs))
+    spec.q, spec.r = (ctypes.c_float * 12)(*qs), (ctypes.c_float * 4)(*rs)
+    spec.terminal, spec.reward_scale = float(terminal), float(reward_scale)
+    return spec, keep
+
+
+def _check_track(swarm, track):
+    """`track` as (spec, keep) from `track_spec`, held against the swarm's shape."""
+    spec, keep = track
+    ref = keep[0]
+    if ref.device != swarm.device or tuple(ref.shape[1:3]) != (swarm.num_envs, swarm.num_drones):
+        raise ValueError(f"track: ref must be (L, {swarm.num_envs}, {swarm.num_drones}, 12) on {swarm.device}")
+    return spec
+
+
+class _Tracking:
+    """What `MPPIPlanner` and `CEMPlanner` add for a tracking cost (qs_track_mppi_* /
+    qs_track_cem_*: set, buffers, score; include/quadswarm.h)."""
+
+    cost_agent = None   # (C, E, D) float64, while a tracking spec is attached
+    _track_keep = None
+
+    def _track_fn(self, name):
+        fn = f"qs_track_{self._PREFIX[3:]}_{name}"
+        if not hasattr(self.lib, fn):
+            raise L.QuadSwarmError(f"{L.LIB_PATH} has no {fn}: rebuild the HIP extension")
+        return fn
+
+    def set_tracking(self, ref, q, r=0.0, terminal=1.0, reward_scale=1.0, base=None):
+        """Plan on a tracking objective: the score stage sums, per drone, the cost of
+        `track_spec` inside the score launch and folds it, so `ret` becomes
+        reward_scale · ret − mean_d cost and `ret_agent` reward_scale · ret_agent − cost;
+        update, select and refit consume that unchanged.  Afterwards `cost_agent` and
+        `ret_agent` (C, E, D) float64 view the planner's buffers.  The planner keeps
+        the tensors alive and reads them at every launch.  A host call: not to be
+        captured.  Refused next to a value tail; a refusal leaves the planner as it was."""
+        sw = self.swarm
+        track = track_spec(ref, q, r, terminal, reward_scale, base)
+        spec, fn = _check_track(sw, track), self._track_fn("set")
+        with torch.cuda.device(sw.device):
+            L.check(getattr(self.lib, fn)(self._p, ctypes.byref(spec)), fn)
+        self._track_keep = track
+        self._track_views()
+
+    def clear_tracking(self):
+        """Detach the tracking spec: the planner scores by the task's reward again."""
+        fn = self._track_fn("set")
+        with torch.cuda.device(self.swarm.device):
+            L.check(getattr(self.lib, fn)(self._p, None), fn)
+        self._track_keep = None
+        self._track_views()
+
+    def _track_views(self):
+        sw, fn = self.swarm, self._track_fn("buffers")
+        cost, ra = ctypes.c_void_p(), ctypes.c_void_p()
+        L.check(getattr(self.lib, fn)(self._p, ctypes.byref(cost), ctypes.byref(ra)), fn)
+        shape = (self.num_candidates, sw.num_envs, sw.num_drones)
+        self.cost_agent = torch.as_tensor(_DeviceSpan(cost.value, shape, "<f8"), device=sw.device) if cost.value else None
+        if not self.per_drone:   # (a per-drone planner's ret_agent is its own, with or without tracking)
+            self.ret_agent = torch.as_tensor(_DeviceSpan(ra.value, shape, "<f8"), device=sw.device) if ra.value else None
+
+    def track(self):
+        """The scoring stage of `plan()` on its own, as it runs with the attached
+        tracking spec: `cost_agent` and the folded `ret` / `ret_agent` of the
+        candidates from the swarm's current state (without a spec: the plain score)."""
+        fn = self._track_fn("score")
+        L.check(getattr(self.lib, fn)(self._p, self._stream()), fn)
+
+
 def prior_spec(actor, count, obs, obs_normalizer=None, std_scale=1.0, device=None, action_scale=None):
     """The `QsPriorSpec` of a policy prior (include/quadswarm.h qs_prior_spec) and the
     tensors it points into, which the caller keeps alive as long as the spec is used.
@@ -1012,7 +1128,7 @@ class _Sampling:
         self._sampling_set(None)
 
 
-class MPPIPlanner(_Sampling, _PolicyPrior, _ValueTail, _Planner):
+class MPPIPlanner(_Tracking, _Sampling, _PolicyPrior, _ValueTail, _Planner):
     """The native MPPI tick round `QuadSwarm.score` (qs_mppi_*, include/quadswarm.h).
 
     `sample()` draws `candidates` sequences round `nominal` (candidate 0 is the
@@ -1050,7 +1166,13 @@ class MPPIPlanner(_Sampling, _PolicyPrior, _ValueTail, _Planner):
 
     `set_sampling(rho)` makes the noise of every candidate an AR(1) sequence along
     the steps, in the same number of launches; `clear_sampling()` undoes it
-    (`_Sampling`)."""
+    (`_Sampling`).
+
+    `set_tracking(ref, q, r, terminal, reward_scale, base)` makes the objective a
+    quadratic tracking cost against a reference, summed inside the score launch
+    and folded into `ret` / `ret_agent` by one more launch; `track()` is that stage
+    on its own, `cost_agent` its result and `clear_tracking()` undoes it
+    (`_Tracking`; not together with `set_value`)."""
 
     _PREFIX = "qs_mppi"
 
@@ -1082,7 +1204,7 @@ class MPPIPlanner(_Sampling, _PolicyPrior, _ValueTail, _Planner):
         self._call("update")
 
 
-class CEMPlanner(_Sampling, _PolicyPrior, _ValueTail, _Planner):
+class CEMPlanner(_Tracking, _Sampling, _PolicyPrior, _ValueTail, _Planner):
     """The native CEM tick round `QuadSwarm.score` (qs_cem_*, include/quadswarm.h).
 
     `begin()` restarts the spread `std` at sigma; `sample(i)` draws `candidates`
