@@ -964,6 +964,74 @@ int qs_track_cem_set(qs_cem* p, const qs_track_spec* spec);
 int qs_track_cem_buffers(const qs_cem* p, double** cost_agent, double** ret_agent);
 int qs_track_cem_score(qs_cem* p, void* stream);
 
+/* Separation and obstacle terms: two more parts of the cost that qs_track_score sums,
+ * for collision-free formation changes and obstacle avoidance.  (New entry points of
+ * ABI 4; every name starts with qs_avoid_.  The qs_track_ names and records stand.)
+ *
+ * The terms.  For candidate c, env e, drone d, at every step j = 0 .. jd (jd as for
+ * ret_agent), with p_i the three floats the obs row of drone i of the same virtual
+ * env starts with after step j and before any auto-reset (obs[..., 0:3], or
+ * terminal_obs[..., 0:3] on a done step; on fp64 handles too), all in double, every
+ * subtraction, product and sum rounded on its own (no fused multiply-add):
+ *   separation (skipped where sep_weight == 0, sep_radius == 0 or D == 1):
+ *     r2 = sep_radius * sep_radius;  s_sep = 0
+ *     for i in 0..D-1, i != d:
+ *       dx = p_d[0] - p_i[0];  dy = p_d[1] - p_i[1];  dz = (p_d[2] - p_i[2]) * sep_z_scale
+ *       d2 = (dx * dx + dy * dy) + dz * dz;  g = r2 - d2
+ *       if g > 0: s_sep = s_sep + g * g          (a NaN compares false: no term)
+ *   obstacles (skipped where M == 0); row m of the table is c[3], a[3], radius, weight:
+ *     s_obs = 0
+ *     for m in 0..M-1:
+ *       d2 = 0;  for k in 0..2: dd = p_d[k] - c[k];  d2 = d2 + a[k] * (dd * dd)
+ *       g = radius * radius - d2
+ *       if g > 0: s_obs = s_obs + weight * (g * g)
+ *   the step's cost: s as in qs_track_score (terminal and the action terms included;
+ *   +0.0 without a tracking spec), then s = s + sep_weight * s_sep, then s = s + s_obs;
+ *   cost_agent[c][e][d] += s.
+ * The avoidance terms are not scaled by `terminal`.  An axis weight of 0 drops an axis:
+ * a = (1, 1, 1) is a sphere, (1, 1, 0) a vertical cylinder, (0, 0, 1) a slab such as a
+ * floor or a ceiling.  A pair contributes to both of its drones, so the fold's mean over
+ * D counts a pair twice over D.
+ *
+ *  - obstacles is the caller's device memory, shared by all envs and candidates, read at
+ *    every launch and never copied: an update in place is seen by the next launch, or the
+ *    next replay of a captured one.  Its contents are not validated.
+ *  - qs_avoid_score is qs_track_score with the two terms; track may be NULL (no tracking
+ *    part: nothing of a reference is read).  With every switch off and a tracking spec,
+ *    cost_agent is qs_track_score's, byte for byte; every other output is what
+ *    qs_track_score (track == NULL: qs_score_agents) writes.
+ *  - qs_avoid_mppi_set / qs_avoid_cem_set copy the spec (NULL detaches), independently of
+ *    a tracking spec.  The score stage of plan() is then qs_avoid_score with the planner's
+ *    tracking spec or NULL, and qs_track_fold with that spec's reward_scale, or 1.
+ *    *_score is that stage on its own; *_buffers returns cost_agent and the ret_agent in
+ *    use (NULL with neither spec).  The set calls are host calls that may synchronise.
+ *    Avoidance and the value tail do not compose: the second to be attached is refused.
+ *    Branch sets and the particle tick have none of this.
+ *
+ * Refusals (QS_E_INVALID, the entry point's name first; nothing is written): a null
+ * handle, avoid or cost_agent; M outside 0 .. 16; obstacles NULL or not 16-byte aligned
+ * where M > 0; sep_radius, sep_weight or sep_z_scale negative or not finite; whatever
+ * qs_track_score refuses, where track is given; cost_agent overlapping an output or an
+ * action buffer.                                                                   */
+typedef struct qs_avoid_spec {
+  const float* obstacles;   /* device [M][8] float32: c[3], a[3], radius, weight; the caller's, read at every launch; 16-byte aligned */
+  int32_t M;                /* 0 .. 16 rows */
+  float sep_radius;         /* finite, >= 0; 0 switches the separation term off */
+  float sep_weight;         /* finite, >= 0; 0 switches the separation term off */
+  float sep_z_scale;        /* finite, >= 0: the factor on the height difference of a pair */
+} qs_avoid_spec;
+
+int qs_avoid_score(qs_handle* h, int n, int C, const float* const* actions,
+                   const qs_step_out* outs, const qs_score_out* score, double* ret_agent,
+                   const qs_track_spec* track /* may be NULL */, const qs_avoid_spec* avoid,
+                   double* cost_agent, void* stream);
+int qs_avoid_mppi_set(qs_mppi* p, const qs_avoid_spec* spec);
+int qs_avoid_mppi_buffers(const qs_mppi* p, double** cost_agent, double** ret_agent);
+int qs_avoid_mppi_score(qs_mppi* p, void* stream);
+int qs_avoid_cem_set(qs_cem* p, const qs_avoid_spec* spec);
+int qs_avoid_cem_buffers(const qs_cem* p, double** cost_agent, double** ret_agent);
+int qs_avoid_cem_score(qs_cem* p, void* stream);
+
 /* Particle (sequential Monte Carlo) planner tick on top of a branch set: fork C
  * particles from the handle's current state, run the horizon in S = ceil(n / L)
  * segments of at most L steps, each "sample actions, advance the particles, weigh

@@ -335,6 +335,18 @@ int qs_sampling_mppi_set(qs_mppi* p, const qs_sampling_spec* spec) {
   return qs::sampling_attach("qs_sampling_mppi_set", p, qs::kSamplingMppi, 0, spec);
 }
 
+int qs_avoid_mppi_set(qs_mppi* p, const qs_avoid_spec* spec) { return qs::avoid_attach("qs_avoid_mppi_set", p, spec); }
+
+int qs_avoid_mppi_buffers(const qs_mppi* p, double** cost_agent, double** ret_agent) {
+  return qs::track_buffers("qs_avoid_mppi_buffers", p, cost_agent, ret_agent);
+}
+
+int qs_avoid_mppi_score(qs_mppi* p, void* stream) {
+  if (!p) return qs::set_last_error(QS_E_INVALID, "qs_avoid_mppi_score: null planner");
+  if (int rc = qs::planner_ready("qs_avoid_mppi_score", p)) return rc;
+  return qs::planner_score(p, p->buf[qs::kMppiRet], p->buf[qs::kMppiFirstDone], stream);
+}
+
 int qs_track_mppi_set(qs_mppi* p, const qs_track_spec* spec) { return qs::track_attach("qs_track_mppi_set", p, spec); }
 
 int qs_track_mppi_buffers(const qs_mppi* p, double** cost_agent, double** ret_agent) {

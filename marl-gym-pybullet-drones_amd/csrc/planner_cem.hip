@@ -565,6 +565,18 @@ int qs_prior_cem_rollout(qs_cem* p, void* stream) {
   return prior_impl(p, stream);
 }
 
+int qs_avoid_cem_set(qs_cem* p, const qs_avoid_spec* spec) { return qs::avoid_attach("qs_avoid_cem_set", p, spec); }
+
+int qs_avoid_cem_buffers(const qs_cem* p, double** cost_agent, double** ret_agent) {
+  return qs::track_buffers("qs_avoid_cem_buffers", p, cost_agent, ret_agent);
+}
+
+int qs_avoid_cem_score(qs_cem* p, void* stream) {
+  if (!p) return qs::set_last_error(QS_E_INVALID, "qs_avoid_cem_score: null planner");
+  if (int rc = qs::planner_ready("qs_avoid_cem_score", p)) return rc;
+  return qs::planner_score(p, p->buf[qs::kCemRet], p->buf[qs::kCemFirstDone], stream);
+}
+
 int qs_track_cem_set(qs_cem* p, const qs_track_spec* spec) { return qs::track_attach("qs_track_cem_set", p, spec); }
 
 int qs_track_cem_buffers(const qs_cem* p, double** cost_agent, double** ret_agent) {

@@ -247,7 +247,7 @@ struct PlannerBase {
   ValueState* value = nullptr;       // qs_value_mppi_set / qs_value_cem_set; null: the plain score
   PriorState* prior = nullptr;       // qs_prior_mppi_set / qs_prior_cem_set; null: every candidate is sampled
   SamplingState* sampling = nullptr; // qs_sampling_*_set; null: white noise and no elite memory
-  TrackState* track = nullptr;       // qs_track_mppi_set / qs_track_cem_set; null: the task's reward alone
+  TrackState* track = nullptr;       // qs_track_*_set / qs_avoid_*_set; null: the task's reward alone
   int units() const { return per_drone ? E * D : E; }      // what the kernels take for envs
   int row() const { return per_drone ? A : D * A; }        // components of a unit's row
   int fd_div() const { return per_drone ? D : 1; }         // units per entry of first_done
@@ -333,6 +333,10 @@ int prior_count(const PlannerBase* p);   // the attached prior's candidates per 
 void track_release(PlannerBase* p);
 int track_attach(const char* who, PlannerBase* p, const qs_track_spec* spec);
 bool track_attached(const PlannerBase* p);
+// The separation and obstacle terms (planner_track.hip): avoid_attach copies the spec
+// next to the tracking one, or on its own, and shares its buffers and its score stage.
+int avoid_attach(const char* who, PlannerBase* p, const qs_avoid_spec* spec);
+bool avoid_attached(const PlannerBase* p);
 int track_buffers(const char* who, const PlannerBase* p, double** cost_agent, double** ret_agent);
 int track_score(PlannerBase* p, void* ret, void* first_done, void* stream);
 

@@ -240,6 +240,9 @@ int value_attach(const char* who, PlannerBase* p, const qs_value_spec* spec) {
   if (track_attached(p))
     return set_last_error(QS_E_INVALID, std::string(who) + ": a tracking spec is attached: the tail's discounted return and "
                                                            "the undiscounted tracking cost do not compose (detach it first)");
+  if (avoid_attached(p))
+    return set_last_error(QS_E_INVALID, std::string(who) + ": an avoidance spec is attached: the tail's discounted return and "
+                                                           "the undiscounted avoidance cost do not compose (detach it first)");
   qs_dims d;
   if (int rc = qs_get_dims(p->h, &d)) return rc;
   const ValueShape shape{p->n, p->C, p->E, p->D, d.obs_dim, d.precision};

@@ -22,6 +22,7 @@
 #include "step_fuse.h"
 #include "step_score.h"
 #include "track_sizes.h"
+#include "avoid_sizes.h"
 #include "step_branch.h"
 #include "step_trunc.h"
 #include "planner_link.h"
@@ -373,7 +374,8 @@ static qs::HotShape hot_shape_of(const qs_handle* h, const qs::ParamsMany<T>& P,
 // has capped P.nsteps by seq_depth); FUSE = 3: the FUSE = 2 launch over P.E
 // virtual envs (qs_score, P.nsteps within score_depth); FUSE = 4: that launch on a
 // branch set's own blocks (qs_branch_advance); FUSE = 5: the FUSE = 3 launch with a
-// tracking cost (qs_track_score).  select_only: no launch.
+// tracking cost (qs_track_score); FUSE = 6: that launch with separation and obstacle
+// terms (qs_avoid_score).  select_only: no launch.
 template <class T, int FUSE>
 static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t st, LaunchInfo* info, bool select_only,
                          int* kind = nullptr) {
@@ -407,7 +409,7 @@ static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t
       }
     }
   }
-  if constexpr (FUSE == 2 || FUSE == 3 || FUSE == 4 || FUSE == 5) {
+  if constexpr (FUSE == 2 || FUSE == 3 || FUSE == 4 || FUSE == 5 || FUSE == 6) {
     lds = seq_lds_base(h, lds) + (size_t)P.nsteps * qs::kSeqStepBytes * (size_t)h->dims.act_dim;
     if (lds + kLdsStatic > kLdsBytes) return fail(QS_E_INVALID, "launch: the steps' action rows do not fit in LDS");
   }
@@ -419,7 +421,7 @@ static int launch_kernel(qs_handle* h, qs::KernelParams<T, FUSE>& P, hipStream_t
   else if (s.task == QS_TASK_SPIRAL)
     ok = qs::launch_task<T, QS_TASK_SPIRAL, FUSE>(s.act_type, grid, lds, st, P, s.ctrl_freq, s.pyb_freq, s.physics, &fn,
                                                   select_only);
-  else if constexpr (FUSE == 2 || FUSE == 3 || FUSE == 4 || FUSE == 5)
+  else if constexpr (FUSE == 2 || FUSE == 3 || FUSE == 4 || FUSE == 5 || FUSE == 6)
     return fail(QS_E_INVALID, "launch: no action-sequence instances of the Flock / Meetup / LeaderFollower family");
   else
     ok = qs::launch_task<T, qs::kTaskMarl, FUSE>(s.act_type, grid, lds, st, P, s.ctrl_freq, s.pyb_freq, s.physics, &fn,
@@ -773,11 +775,13 @@ static int score_depth(const qs_handle* h) {
   return qs::score_depth(kSeqLdsMax, kLdsStatic + kLdsGrain, image, plan - hist, h->dims.act_dim);
 }
 
-// `who`: the entry point, qs_score, qs_score_agents or qs_track_score; ret_agent: the latter two's extra
-// output, or null; track / cost_agent: qs_track_score's spec (checked by the caller) and its output, or both null.
+// `who`: the entry point, qs_score, qs_score_agents, qs_track_score or qs_avoid_score; ret_agent: the latter
+// three's extra output, or null; track / cost_agent: qs_track_score's spec (checked by the caller) and its output,
+// or both null; avoid: qs_avoid_score's spec (checked by the caller; its track may be null), or null.
 template <class T> static int score_impl(const char* who_c, qs_handle* h, int n, int C, const float* const* actions,
                                          const qs_step_out* outs, const qs_score_out* score, double* ret_agent,
-                                         const qs_track_spec* track, double* cost_agent, hipStream_t st) {
+                                         const qs_track_spec* track, double* cost_agent, const qs_avoid_spec* avoid,
+                                         hipStream_t st) {
   const std::string who = std::string(who_c) + ": ";
   const qs_dims& d = h->dims;
   uint64_t bytes[qs::kScoreOuts], act_bytes = 0;
@@ -820,9 +824,8 @@ template <class T> static int score_impl(const char* who_c, qs_handle* h, int n,
     if (!qs::score_fits(cb))
       return fail(QS_E_INVALID, who + "cost_agent of C * num_envs * num_drones doubles is too large (32-bit offsets)");
     // (held against every range by hand: ScoreRanges has room for qs_score_agents' ranges only)
-    const uintptr_t lo = (uintptr_t)cost_agent, hi = lo + (uintptr_t)cb;
     for (int i = 0; i < ranges.n; ++i)
-      if (lo < ranges.r[i].hi && ranges.r[i].lo < hi)
+      if (qs::avoid_ranges_meet((uintptr_t)cost_agent, cb, ranges.r[i].lo, ranges.r[i].hi))
         return fail(QS_E_INVALID, who + "cost_agent overlaps another output or an action buffer");
   }
   if (!any_out) return fail(QS_E_INVALID, who + "nothing to write (no output in outs[] and neither ret nor first_done)");
@@ -843,9 +846,7 @@ template <class T> static int score_impl(const char* who_c, qs_handle* h, int n,
     if (score) { P.ret = (double*)score->ret; P.first_done = score->first_done; }
     P.ret_agent = ret_agent;
   };
-  if (track) {   // the FUSE = 5 instance: the same launch plus the cost
-    qs::ParamsTrack<T> P;
-    std::memset(&P, 0, sizeof(P));
+  auto fill_track = [&](qs::ParamsTrack<T>& P) {
     fill(P);
     P.ref = track->ref;
     P.base = track->base;
@@ -854,6 +855,29 @@ template <class T> static int score_impl(const char* who_c, qs_handle* h, int n,
     for (int k = 0; k < qs::kTrackMaxAct; ++k) P.r[k] = k < d.act_dim ? track->r[k] : 0.0f;
     P.terminal = track->terminal;
     P.cost_agent = cost_agent;
+  };
+  if (avoid) {   // the FUSE = 6 instance: the tracking launch, or one without a reference, plus the avoidance terms
+    static_assert(qs::kAvoidMaxRows == qs::kAvoidMaxObs, "the table's rows: avoid_sizes.h and step_kernel.h");
+    qs::ParamsAvoid<T> P;
+    std::memset(&P, 0, sizeof(P));
+    if (track) {
+      fill_track(P);
+    } else {   // ref stays null: the kernel reads no reference and sums no tracking term
+      fill(P);
+      P.L = 1;
+      P.cost_agent = cost_agent;
+    }
+    P.obstacles = avoid->M > 0 ? avoid->obstacles : nullptr;
+    P.M = avoid->M;
+    P.sep_radius = avoid->sep_radius;
+    P.sep_weight = avoid->sep_weight;
+    P.sep_z_scale = avoid->sep_z_scale;
+    return launch_kernel<T, 6>(h, P, st, nullptr, false);
+  }
+  if (track) {   // the FUSE = 5 instance: the same launch plus the cost
+    qs::ParamsTrack<T> P;
+    std::memset(&P, 0, sizeof(P));
+    fill_track(P);
     return launch_kernel<T, 5>(h, P, st, nullptr, false);
   }
   qs::ParamsScore<T> P;
@@ -1285,16 +1309,29 @@ static const char* track_refusal_text(const qs_handle* h, const qs_track_spec* s
   }
 }
 
-// qs_score, qs_score_agents (ret_agent null: the same call under the other name) and qs_track_score
-// (tracking: spec and cost_agent must be there).
+// Why an avoidance spec is refused (avoid_sizes.h), as the message after the entry point's name.
+static const char* avoid_refusal_text(const qs_avoid_spec* s) {
+  const qs::AvoidSpecShape v{(uintptr_t)s->obstacles, s->M, s->sep_radius, s->sep_weight, s->sep_z_scale};
+  return qs::avoid_refusal_text(qs::avoid_refusal(v));
+}
+
+// qs_score, qs_score_agents (ret_agent null: the same call under the other name), qs_track_score
+// (tracking: spec and cost_agent must be there) and qs_avoid_score (avoiding: avoid and cost_agent must be
+// there, track may be null).
 static int score_entry(const char* who_c, qs_handle* h, int n, int C, const float* const* actions, const qs_step_out* outs,
                        const qs_score_out* score, double* ret_agent, void* stream, bool tracking = false,
-                       const qs_track_spec* track = nullptr, double* cost_agent = nullptr) {
+                       const qs_track_spec* track = nullptr, double* cost_agent = nullptr, bool avoiding = false,
+                       const qs_avoid_spec* avoid = nullptr) {
   const std::string who = std::string(who_c) + ": ";
   if (!h) return fail(QS_E_INVALID, who + "null handle");
   if (tracking) {
     if (!track) return fail(QS_E_INVALID, who + "spec is null");
     if (!cost_agent) return fail(QS_E_INVALID, who + "cost_agent is null");
+  }
+  if (avoiding) {
+    if (!avoid) return fail(QS_E_INVALID, who + "avoid is null");
+    if (!cost_agent) return fail(QS_E_INVALID, who + "cost_agent is null");
+    tracking = track != nullptr;
   }
   if (const char* why = score_refusal(h)) return fail(QS_E_INVALID, who + "this handle cannot score: " + why);
   const int depth = score_depth(h);
@@ -1308,11 +1345,21 @@ static int score_entry(const char* who_c, qs_handle* h, int n, int C, const floa
     if (!actions[j]) return fail(QS_E_INVALID, who + "actions[" + std::to_string(j) + "] is null");
   if (tracking)
     if (const char* why = track_refusal_text(h, track)) return fail(QS_E_INVALID, who + why);
+  if (avoiding)
+    if (const char* why = avoid_refusal_text(avoid)) return fail(QS_E_INVALID, who + why);
   if (!h->reset_done) return fail(QS_E_STATE, who + "call qs_reset first");
   h->fuse.forget();
   hipStream_t st = (hipStream_t)stream;
-  if (h->dims.precision == 8) return score_impl<double>(who_c, h, n, C, actions, outs, score, ret_agent, track, cost_agent, st);
-  return score_impl<float>(who_c, h, n, C, actions, outs, score, ret_agent, track, cost_agent, st);
+  if (h->dims.precision == 8)
+    return score_impl<double>(who_c, h, n, C, actions, outs, score, ret_agent, track, cost_agent, avoid, st);
+  return score_impl<float>(who_c, h, n, C, actions, outs, score, ret_agent, track, cost_agent, avoid, st);
+}
+
+int qs_avoid_score(qs_handle* h, int n, int C, const float* const* actions, const qs_step_out* outs,
+                   const qs_score_out* score, double* ret_agent, const qs_track_spec* track, const qs_avoid_spec* avoid,
+                   double* cost_agent, void* stream) {
+  return score_entry("qs_avoid_score", h, n, C, actions, outs, score, ret_agent, stream, false, track, cost_agent, true,
+                     avoid);
 }
 
 int qs_track_score(qs_handle* h, int n, int C, const float* const* actions, const qs_step_out* outs,

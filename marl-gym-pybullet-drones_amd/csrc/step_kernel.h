@@ -352,10 +352,30 @@ template <class T> struct ParamsTrack : ParamsScore<T> {
   float q[12], r[4], terminal;
   double* cost_agent;    // [E][D]: each drone's cost up to the env's first done step
 };
+// Arguments of the avoidance instances (step_kernel FUSE = 6, qs_avoid_score): the
+// FUSE = 5 launch whose cost also holds a pairwise separation term among the drones
+// of an env and the terms of a caller-supplied obstacle table (avoid_sizes.h).  The
+// tracking part is optional here: ref == nullptr means no tracking spec, and the
+// kernel then neither loads a reference row nor sums the tracking terms.  A type of
+// its own once more: ParamsTrack keeps its size, and the FUSE = 5 instances their
+// argument blocks and their code.
+template <class T> struct ParamsAvoid : ParamsTrack<T> {
+  const float* obstacles;   // [M][8]: centre[3], axis weights[3], radius, weight; the caller's, 16-byte aligned
+  int M;                    // 0 .. kAvoidMaxObs rows
+  float sep_radius, sep_weight, sep_z_scale;
+};
 template <class T, int FUSE>
-using KernelParams = std::conditional_t<FUSE == 5, ParamsTrack<T>, std::conditional_t<FUSE == 4, ParamsBranch<T>,
-    std::conditional_t<FUSE == 3, ParamsScore<T>,
-    std::conditional_t<FUSE == 2, ParamsSeq<T>, std::conditional_t<FUSE != 0, ParamsMany<T>, Params<T>>>>>>;
+using KernelParams = std::conditional_t<FUSE == 6, ParamsAvoid<T>, std::conditional_t<FUSE == 5, ParamsTrack<T>,
+    std::conditional_t<FUSE == 4, ParamsBranch<T>, std::conditional_t<FUSE == 3, ParamsScore<T>,
+    std::conditional_t<FUSE == 2, ParamsSeq<T>, std::conditional_t<FUSE != 0, ParamsMany<T>, Params<T>>>>>>>;
+constexpr int kAvoidMaxObs = 16;   // rows of an obstacle table (avoid_sizes.h holds the same number)
+
+// The avoidance instances' obstacle table in LDS, two float4 a row (512 bytes; only
+// the kernels that call this get the array).
+__device__ __forceinline__ float4* avoid_table() {
+  __shared__ float4 tab[2 * kAvoidMaxObs];
+  return tab;
+}
 
 // ---------------------------------------------------- conversions (external)
 // pybullet getMatrixFromQuaternion = btMatrix3x3::setRotation (s = 2/|q|²).
@@ -900,6 +920,14 @@ template <class T> __device__ __forceinline__ int launch_src_envs(const ParamsSc
 // the step, before the PID, and read at the reward stage: the substeps hide it.
 // The weights are launch constants held in SGPRs.  Every other statement is the
 // FUSE = 3 instance's, so the other outputs are its bytes.
+// FUSE = 6: the FUSE = 5 launch with separation and obstacle terms (qs_avoid_score,
+// ParamsAvoid).  At the reward stage every lane leaves its position, as the three
+// floats its obs row starts with, in LDS (Shared::dw4, free between the substeps and
+// the reset search) and reads its env's D rows back in order: the squared hinge on
+// the pairwise distance, then the same hinge against every row of the obstacle
+// table, which is staged in LDS once before the loop and read wave-uniformly.  The
+// tracking part runs only where the launch has a reference (wave-uniform).  Every
+// other statement is the FUSE = 5 instance's.
 // HOT = 1 (FUSE = 1, MultiHover, compile-time control frequency, AUXM 0 only):
 // the launch shape qs::hot_shape_ok (step_fuse.h) accepts, with everything that
 // predicate fixes for the launch folded in ("hot shape"): D = 8
@@ -998,7 +1026,9 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
   // draws still go by the source env, v mod E_src.
   // FUSE = 5 (qs_track_score): the FUSE = 3 launch plus the tracking cost.
   constexpr bool kBranch = FUSE == 4;
-  constexpr bool kTrack = FUSE == 5;
+  // FUSE = 6 (qs_avoid_score): that launch plus the separation and obstacle terms.
+  constexpr bool kAvoid = FUSE == 6;
+  constexpr bool kTrack = FUSE == 5 || kAvoid;
   constexpr bool kScore = FUSE == 3 || kTrack || kBranch;
   const int e_h = (kScore && !kBranch) ? e % launch_src_envs(P) : e, a_h = (kScore && !kBranch) ? e_h * D + d : a;
   const uint32_t genv = (uint32_t)(P.env_offset + (kBranch ? e % launch_src_envs(P) : e_h));
@@ -1109,7 +1139,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
   extern __shared__ float4 dyn_lds4[];   // float4: 16-B aligned staging for the obs stores
   // FUSE = 2: the launch's action rows come first, nsteps · A · kBlock floats
   // (a multiple of 256 bytes: the stage keeps its alignment)
-  constexpr bool kSeq = FUSE == 2 || FUSE == 3 || FUSE == 4 || FUSE == 5;
+  constexpr bool kSeq = FUSE == 2 || FUSE == 3 || FUSE == 4 || FUSE == 5 || FUSE == 6;
   float* const dyn_lds = reinterpret_cast<float*>(dyn_lds4);
   float* const act_lds = dyn_lds;
   float* const hist_pref = kSeq ? dyn_lds + (size_t)launch_steps(P) * kBlock * A : dyn_lds;
@@ -1220,6 +1250,25 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
 #pragma unroll
     for (int k = 0; k < A; ++k) track_w[k] = keep_sgpr(P.r[k]);
     track_term = keep_sgpr(P.terminal);
+  }
+  // FUSE = 6: whether the launch tracks at all (no reference: nothing of it is read),
+  // the separation term's numbers as doubles, formed once, and the obstacle table, two
+  // float4 a row, from the caller's memory into LDS (a 16-byte aligned table of M <= 16
+  // rows, avoid_sizes.h; lanes past it load nothing).  A switch that is off skips its
+  // term: nothing is added, not even a zero.
+  [[maybe_unused]] bool track_on = true, sep_on = false;
+  [[maybe_unused]] int avoid_M = 0;
+  [[maybe_unused]] double sep_r2 = 0, sep_w = 0, sep_zs = 0;
+  if constexpr (kAvoid) {
+    track_on = track_ptr != nullptr;
+    avoid_M = keep_sgpr(P.M);
+    const float sr = keep_sgpr(P.sep_radius), sw = keep_sgpr(P.sep_weight);
+    sep_on = sr != 0.0f && sw != 0.0f && D > 1;
+    sep_r2 = __dmul_rn((double)sr, (double)sr);
+    sep_w = (double)sw;
+    sep_zs = (double)keep_sgpr(P.sep_z_scale);
+    if (tid < 2 * avoid_M) avoid_table()[tid] = reinterpret_cast<const float4*>(P.obstacles)[tid];
+    __syncthreads();
   }
   float cur_act[A];            // this step's action (newest history entry)
 #pragma unroll
@@ -1338,7 +1387,11 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
   // and nothing uses what they read.  The loads land under the PID and the substeps
   // and are read at the reward stage.
   [[maybe_unused]] float track_ref[12];
-  if constexpr (kTrack) {
+  if constexpr (kAvoid) {   // (without a reference the row is never loaded and never read)
+#pragma unroll
+    for (int k = 0; k < 12; ++k) track_ref[k] = 0.f;
+  }
+  if constexpr (kTrack) if (kAvoid ? track_on : true) {
     int row = track_base >= track_L ? track_L - 1 : track_base + ks;
     row = row < 0 ? 0 : (row > track_L - 1 ? track_L - 1 : row);
     // (the pointer went through an SGPR pin, which drops its address space: named again, the loads are global, not flat)
@@ -1957,7 +2010,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
       // FUSE = 5: the step's cost of this drone, in double, every product and sum
       // rounded on its own, from the floats the obs row holds (write_obs_row)
       [[maybe_unused]] double track_s = 0;
-      if constexpr (kTrack) {
+      if constexpr (kTrack) if (kAvoid ? track_on : true) {
         const float x[12] = {(float)pos[0], (float)pos[1], (float)pos[2], (float)rpy[0], (float)rpy[1], (float)rpy[2],
                              (float)vel[0], (float)vel[1], (float)vel[2], (float)angv[0], (float)angv[1], (float)angv[2]};
 #pragma unroll
@@ -1969,6 +2022,51 @@ __global__ void __launch_bounds__(kBlock) step_kernel(std::conditional_t<HOT == 
 #pragma unroll
         for (int k = 0; k < A; ++k)
           track_s = __dadd_rn(track_s, __dmul_rn((double)track_w[k], __dmul_rn((double)cur_act[k], (double)cur_act[k])));
+      }
+      // FUSE = 6: the separation and obstacle terms of this drone, from the same floats.
+      // Shared::dw4 carries the positions: the substeps' downwash snapshot is read
+      // out (every writer of the union waits at a barrier first, as this one does), and
+      // the reset search below writes it only behind barriers of its own.  Idle lanes
+      // write a row nobody reads and read none (their env's rows could lie past the array).
+      if constexpr (kAvoid) {
+        const float px = (float)pos[0], py = (float)pos[1], pz = (float)pos[2];
+        if (sep_on) {   // wave-uniform
+          float4* const nb = s.dw4;
+          __syncthreads();
+          nb[tid] = make_float4(px, py, pz, 0.f);
+          __syncthreads();
+          double s_sep = 0;
+          if (valid) {
+            const float4* const en = nb + lenv * D;
+            for (int j = 0; j < D; ++j) {
+              const float4 o4 = en[j];
+              const double dx = __dsub_rn((double)px, (double)o4.x), dy = __dsub_rn((double)py, (double)o4.y);
+              const double dz = __dmul_rn(__dsub_rn((double)pz, (double)o4.z), sep_zs);
+              const double d2 = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+              const double g = __dsub_rn(sep_r2, d2);
+              if (j != d && g > 0.0) s_sep = __dadd_rn(s_sep, __dmul_rn(g, g));
+            }
+          }
+          track_s = __dadd_rn(track_s, __dmul_rn(sep_w, s_sep));
+        }
+        if (avoid_M > 0) {   // wave-uniform, as every address of the table is: broadcast reads
+          const float4* const tab = avoid_table();
+          const float p[3] = {px, py, pz};
+          double s_obs = 0;
+          for (int m = 0; m < avoid_M; ++m) {
+            const float4 t0 = tab[2 * m], t1 = tab[2 * m + 1];
+            const float c[3] = {t0.x, t0.y, t0.z}, ax[3] = {t0.w, t1.x, t1.y};
+            double d2 = 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+              const double dd = __dsub_rn((double)p[k], (double)c[k]);
+              d2 = __dadd_rn(d2, __dmul_rn((double)ax[k], __dmul_rn(dd, dd)));
+            }
+            const double g = __dsub_rn(__dmul_rn((double)t1.z, (double)t1.z), d2);
+            if (g > 0.0) s_obs = __dadd_rn(s_obs, __dmul_rn((double)t1.w, __dmul_rn(g, g)));
+          }
+          track_s = __dadd_rn(track_s, s_obs);
+        }
       }
       if (score_live) {
         score_agent += (double)rterm;

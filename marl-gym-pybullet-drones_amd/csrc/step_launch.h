@@ -11,7 +11,8 @@ namespace qs {
 // steps' actions from ParamsSeq::act[], in further ones; FUSE = 3: the branch
 // rollouts of qs_score (ParamsScore), in theirs; FUSE = 4: those of a branch set
 // (qs_branch_advance, ParamsBranch), in theirs; FUSE = 5: the branch rollouts with a
-// tracking cost (qs_track_score, ParamsTrack), in theirs.  `fn`, if given, receives the kernel's
+// tracking cost (qs_track_score, ParamsTrack), in theirs; FUSE = 6: those with separation and
+// obstacle terms too (qs_avoid_score, ParamsAvoid), in theirs.  `fn`, if given, receives the kernel's
 // function pointer (what a graph kernel node names); `select_only` looks the
 // kernel up without launching it.
 template <class T, int TASK, int FUSE = 0>

@@ -1,8 +1,8 @@
 // step_launch_impl.h — kernel launch dispatch, included by the per-task-family
 // translation units (step_mh.hip, step_spiral.hip, step_marl.hip and their
 // *_fused.hip twins, step_mh_seq.hip, step_spiral_seq.hip, step_mh_score.hip,
-// step_spiral_score.hip, step_mh_branch.hip, step_spiral_branch.hip, step_mh_track.hip
-// and step_spiral_track.hip) so the
+// step_spiral_score.hip, step_mh_branch.hip, step_spiral_branch.hip, step_mh_track.hip,
+// step_spiral_track.hip, step_mh_avoid.hip and step_spiral_avoid.hip) so the
 // kernel instantiations compile in parallel.
 #pragma once
 #include "step_launch.h"

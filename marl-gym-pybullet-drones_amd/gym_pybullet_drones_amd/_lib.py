@@ -124,6 +124,12 @@ class QsTrackSpec(ctypes.Structure):
                 ("r", ctypes.c_float * 4), ("terminal", ctypes.c_float), ("reward_scale", ctypes.c_float)]
 
 
+class QsAvoidSpec(ctypes.Structure):
+    """include/quadswarm.h qs_avoid_spec: the obstacle table and the separation term's numbers."""
+    _fields_ = [("obstacles", ctypes.c_void_p), ("M", ctypes.c_int32), ("sep_radius", ctypes.c_float),
+                ("sep_weight", ctypes.c_float), ("sep_z_scale", ctypes.c_float)]
+
+
 class QsSmcSpec(ctypes.Structure):
     """include/quadswarm.h qs_smc_spec: what a particle (SMC) planner is created from."""
     _fields_ = [("horizon", ctypes.c_int32), ("segment", ctypes.c_int32), ("particles", ctypes.c_int32),
@@ -156,6 +162,8 @@ EXPORTS = ("qs_create", "qs_destroy", "qs_last_error", "qs_abi_version", "qs_get
            "qs_sampling_mppi_set", "qs_sampling_cem_set", "qs_sampling_cem_buffers", "qs_sampling_smc_set",
            "qs_track_score", "qs_track_fold", "qs_track_mppi_set", "qs_track_mppi_buffers", "qs_track_mppi_score",
            "qs_track_cem_set", "qs_track_cem_buffers", "qs_track_cem_score",
+           "qs_avoid_score", "qs_avoid_mppi_set", "qs_avoid_mppi_buffers", "qs_avoid_mppi_score",
+           "qs_avoid_cem_set", "qs_avoid_cem_buffers", "qs_avoid_cem_score",
            "qs_branch_create", "qs_branch_destroy", "qs_branch_buffers", "qs_branch_steps", "qs_branch_fork",
            "qs_branch_advance", "qs_branch_select", "qs_branch_state",
            "qs_smc_create", "qs_smc_destroy", "qs_smc_buffers", "qs_smc_branch", "qs_smc_reset", "qs_smc_begin",
@@ -275,6 +283,13 @@ def load():
             getattr(L, f"qs_track_{who}_set").argtypes = [vp, ctypes.POINTER(QsTrackSpec)]
             getattr(L, f"qs_track_{who}_buffers").argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
             getattr(L, f"qs_track_{who}_score").argtypes = [vp, vp]
+    if hasattr(L, "qs_avoid_score"):   # (a QS_DEV_LIB build from before the entry points: A/B runs)
+        L.qs_avoid_score.argtypes = [vp, i32, i32, ctypes.POINTER(vp), ctypes.POINTER(QsStepOut), ctypes.POINTER(QsScoreOut),
+                                     vp, ctypes.POINTER(QsTrackSpec), ctypes.POINTER(QsAvoidSpec), vp, vp]
+        for who in ("mppi", "cem"):
+            getattr(L, f"qs_avoid_{who}_set").argtypes = [vp, ctypes.POINTER(QsAvoidSpec)]
+            getattr(L, f"qs_avoid_{who}_buffers").argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
+            getattr(L, f"qs_avoid_{who}_score").argtypes = [vp, vp]
     if hasattr(L, "qs_branch_create"):   # (a QS_DEV_LIB build from before the entry points: A/B runs)
         L.qs_branch_create.argtypes = [vp, i32, ctypes.POINTER(vp)]
         L.qs_branch_destroy.argtypes = [vp]
@@ -367,7 +382,7 @@ def load():
     L.qs_rms_normalize.argtypes = [i64, ctypes.c_int32, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp]
     for name in EXPORTS:
         if (name in ("qs_launch_counts", "qs_ring_counts", "qs_score_depth", "qs_score") or name.startswith(("qs_mppi_", "qs_cem_", "qs_pd_", "qs_branch_", "qs_smc_"))
-                or name == "qs_score_agents" or name.startswith(("qs_value_", "qs_prior_", "qs_sampling_", "qs_track_"))) and not hasattr(L, name):
+                or name == "qs_score_agents" or name.startswith(("qs_value_", "qs_prior_", "qs_sampling_", "qs_track_", "qs_avoid_"))) and not hasattr(L, name):
             continue   # (a QS_DEV_LIB build from before the entry point)
         if name not in ("qs_last_error", "qs_learner_last_error", "qs_rms_last_error", "qs_ppo_small_last_error",
                         "qs_rollout_last_error"):

@@ -275,7 +275,8 @@ class QuadSwarm:
 
     _SCORE_OUTS = ("obs", "reward", "terminated", "truncated", "terminal_obs", "reasons", "actions_out")
 
-    def score(self, actions, outs=None, *, ret=None, first_done=None, ret_agent=None, track=None, cost_agent=None):
+    def score(self, actions, outs=None, *, ret=None, first_done=None, ret_agent=None, track=None, cost_agent=None,
+              avoid=None):
         """Run C candidate action sequences of n steps each from the swarm's current
         state in one launch, and leave the swarm exactly as it was (qs_score): no
         state, history, episode log or counter changes.  Virtual env (c, e) starts
@@ -297,7 +298,11 @@ class QuadSwarm:
         track, cost_agent: a `track_spec(...)` result and a (C, E, D) float64 tensor
         (both or neither): the same launch also sums each drone's tracking cost
         against the spec's reference over the same steps (qs_track_score); every
-        other output is the bytes it is without."""
+        other output is the bytes it is without.
+
+        avoid: an `avoid_spec(...)` result, with cost_agent and with or without
+        track: cost_agent also holds the pairwise separation term among an env's
+        drones and the terms of the spec's obstacle table (qs_avoid_score)."""
         E, D, A, O = self.num_envs, self.num_drones, self.act_dim, self.obs_dim
         if isinstance(actions, torch.Tensor):
             if actions.dim() != 5:
@@ -343,6 +348,17 @@ class QuadSwarm:
         if ret is not None or first_done is not None:
             so = ctypes.byref(L.QsScoreOut(buf(ret, "ret"), buf(first_done, "first_done")))
         ptrs = (ctypes.c_void_p * n)(*[a.data_ptr() for a in acts])
+        if avoid is not None:
+            if cost_agent is None:
+                raise ValueError("avoid and cost_agent go together")
+            if not hasattr(self.lib, "qs_avoid_score"):
+                raise L.QuadSwarmError(f"{L.LIB_PATH} has no qs_avoid_score: rebuild the HIP extension")
+            tspec = ctypes.byref(_check_track(self, track)) if track is not None else None
+            aspec = _check_avoid(self, avoid)
+            L.check(self.lib.qs_avoid_score(self._h, n, C, ptrs, arr, so, buf(ret_agent, "ret_agent"), tspec,
+                                            ctypes.byref(aspec), buf(cost_agent, "cost_agent"), self._stream()),
+                    "qs_avoid_score")
+            return
         if (track is None) != (cost_agent is None):
             raise ValueError("track and cost_agent go together")
         if track is not None:
@@ -948,6 +964,95 @@ class _Tracking:
         L.check(getattr(self.lib, fn)(self._p, self._stream()), fn)
 
 
+def avoid_spec(obstacles=None, sep_radius=0.0, sep_weight=0.0, sep_z_scale=1.0):
+    """The `QsAvoidSpec` of the separation and obstacle terms (include/quadswarm.h
+    qs_avoid_spec) and the tensors it points into, which the caller keeps alive as long
+    as the spec is used.
+
+    obstacles: None (no obstacle term) or an (M, 8) float32 tensor on the GPU, M up to
+    16, contiguous and 16-byte aligned, a row being centre (3), axis weights (3), radius,
+    weight: the drone pays weight · max(0, radius² − Σ_k a_k (p_k − c_k)²)² a step.  Axis
+    weights (1, 1, 1) make a sphere, (1, 1, 0) a vertical cylinder, (0, 0, 1) a slab such
+    as a floor or a ceiling.  The table is shared by all envs and candidates; nothing is
+    copied: `obstacles.copy_(...)` is seen by the next launch, also by the next replay of
+    a captured one.  sep_radius, sep_weight, sep_z_scale: every other drone of the env
+    closer than sep_radius (height differences times sep_z_scale) costs
+    sep_weight · (sep_radius² − d²)² a step; a radius or weight of 0 switches the term
+    off.  All finite and >= 0 (the library refuses others)."""
+    spec, keep = L.QsAvoidSpec(), []
+    if obstacles is not None:
+        if (not isinstance(obstacles, torch.Tensor) or obstacles.dtype != torch.float32 or obstacles.dim() != 2
+                or obstacles.shape[-1] != 8 or not obstacles.is_contiguous() or not obstacles.is_cuda):
+            raise ValueError("obstacles must be a contiguous float32 (M, 8) tensor on the GPU")
+        if obstacles.shape[0] > 0:
+            if obstacles.data_ptr() % 16 != 0:
+                raise ValueError("obstacles must be 16-byte aligned")
+            spec.obstacles = obstacles.data_ptr()
+        spec.M = int(obstacles.shape[0])
+        keep.append(obstacles)
+    spec.sep_radius, spec.sep_weight, spec.sep_z_scale = float(sep_radius), float(sep_weight), float(sep_z_scale)
+    return spec, keep
+
+
+def _check_avoid(swarm, avoid):
+    """`avoid` as (spec, keep) from `avoid_spec`, held against the swarm's device."""
+    spec, keep = avoid
+    for t in keep:
+        if t.device != swarm.device:
+            raise ValueError(f"avoid: obstacles must be on {swarm.device}")
+    return spec
+
+
+class _Avoidance:
+    """What `MPPIPlanner` and `CEMPlanner` add for the separation and obstacle terms
+    (qs_avoid_mppi_* / qs_avoid_cem_*: set, buffers, score; include/quadswarm.h).  The
+    spec attaches and detaches independently of a tracking spec (`_Tracking`), and the
+    two share `cost_agent`, `ret_agent` and the score stage."""
+
+    _avoid_keep = None
+
+    def _avoid_fn(self, name):
+        fn = f"qs_avoid_{self._PREFIX[3:]}_{name}"
+        if not hasattr(self.lib, fn):
+            raise L.QuadSwarmError(f"{L.LIB_PATH} has no {fn}: rebuild the HIP extension")
+        return fn
+
+    def set_avoidance(self, obstacles=None, sep_radius=0.0, sep_weight=0.0, sep_z_scale=1.0):
+        """Plan with the terms of `avoid_spec` in the cost: the score stage sums them per
+        drone inside the score launch, after the tracking cost where a tracking spec is
+        attached too, and folds the cost as `set_tracking` describes (with reward_scale 1
+        without a tracking spec).  A pair of drones counts for both, so an env-level
+        planner sees a pair twice over D; a per-drone planner with a separation term
+        optimises every drone against the others' candidate of the same index, the same
+        kind of approximation as for downwash.  Afterwards `cost_agent` and `ret_agent`
+        (C, E, D) float64 view the planner's buffers.  The planner keeps `obstacles`
+        alive and reads it at every launch.  A host call: not to be captured.  Refused
+        next to a value tail; a refusal leaves the planner as it was."""
+        sw = self.swarm
+        avoid = avoid_spec(obstacles, sep_radius, sep_weight, sep_z_scale)
+        spec, fn = _check_avoid(sw, avoid), self._avoid_fn("set")
+        with torch.cuda.device(sw.device):
+            L.check(getattr(self.lib, fn)(self._p, ctypes.byref(spec)), fn)
+        self._avoid_keep = avoid
+        self._track_views()
+
+    def clear_avoidance(self):
+        """Detach the avoidance spec: the planner scores as it did without it (by the
+        tracking objective, where a tracking spec is attached)."""
+        fn = self._avoid_fn("set")
+        with torch.cuda.device(self.swarm.device):
+            L.check(getattr(self.lib, fn)(self._p, None), fn)
+        self._avoid_keep = None
+        self._track_views()
+
+    def avoid(self):
+        """The scoring stage of `plan()` on its own, as it runs with the attached specs:
+        `cost_agent` and the folded `ret` / `ret_agent` of the candidates from the
+        swarm's current state (with neither spec: the plain score)."""
+        fn = self._avoid_fn("score")
+        L.check(getattr(self.lib, fn)(self._p, self._stream()), fn)
+
+
 def prior_spec(actor, count, obs, obs_normalizer=None, std_scale=1.0, device=None, action_scale=None):
     """The `QsPriorSpec` of a policy prior (include/quadswarm.h qs_prior_spec) and the
     tensors it points into, which the caller keeps alive as long as the spec is used.
@@ -1128,7 +1233,7 @@ class _Sampling:
         self._sampling_set(None)
 
 
-class MPPIPlanner(_Tracking, _Sampling, _PolicyPrior, _ValueTail, _Planner):
+class MPPIPlanner(_Avoidance, _Tracking, _Sampling, _PolicyPrior, _ValueTail, _Planner):
     """The native MPPI tick round `QuadSwarm.score` (qs_mppi_*, include/quadswarm.h).
 
     `sample()` draws `candidates` sequences round `nominal` (candidate 0 is the
@@ -1172,7 +1277,12 @@ class MPPIPlanner(_Tracking, _Sampling, _PolicyPrior, _ValueTail, _Planner):
     quadratic tracking cost against a reference, summed inside the score launch
     and folded into `ret` / `ret_agent` by one more launch; `track()` is that stage
     on its own, `cost_agent` its result and `clear_tracking()` undoes it
-    (`_Tracking`; not together with `set_value`)."""
+    (`_Tracking`; not together with `set_value`).
+
+    `set_avoidance(obstacles, sep_radius, sep_weight, sep_z_scale)` adds a pairwise
+    separation term among an env's drones and the terms of an obstacle table to that
+    cost, with or without tracking; `avoid()` is the stage on its own and
+    `clear_avoidance()` undoes it (`_Avoidance`; not together with `set_value`)."""
 
     _PREFIX = "qs_mppi"
 
@@ -1204,7 +1314,7 @@ class MPPIPlanner(_Tracking, _Sampling, _PolicyPrior, _ValueTail, _Planner):
         self._call("update")
 
 
-class CEMPlanner(_Tracking, _Sampling, _PolicyPrior, _ValueTail, _Planner):
+class CEMPlanner(_Avoidance, _Tracking, _Sampling, _PolicyPrior, _ValueTail, _Planner):
     """The native CEM tick round `QuadSwarm.score` (qs_cem_*, include/quadswarm.h).
 
     `begin()` restarts the spread `std` at sigma; `sample(i)` draws `candidates`
@@ -1239,7 +1349,10 @@ class CEMPlanner(_Tracking, _Sampling, _PolicyPrior, _ValueTail, _Planner):
     (n, keep, E, D, A): they re-enter the next sample as candidates 1 .. keep
     (`kept_n` (1,) int32 says how many: 0 until the first refit after a reset), and
     `finish()` shifts them by one step with the mean, so a good sequence found once
-    is not lost to resampling.  `clear_sampling()` undoes it (`_Sampling`)."""
+    is not lost to resampling.  `clear_sampling()` undoes it (`_Sampling`).
+
+    `set_tracking(...)` and `set_avoidance(...)` set the objective as they do for
+    `MPPIPlanner` (`_Tracking`, `_Avoidance`)."""
 
     _PREFIX = "qs_cem"
 

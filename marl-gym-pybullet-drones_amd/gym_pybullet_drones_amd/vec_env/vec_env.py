@@ -194,7 +194,7 @@ class SwarmVecEnv(VecEnv):
         sw.step_many([{k: v[j] for k, v in out.items()} for j in range(n)], actions=actions)
         return out["obs"], out["reward"], out["terminated"], out["truncated"]
 
-    def score_t(self, actions, per_step=False, per_drone=False, track=None):
+    def score_t(self, actions, per_step=False, per_drone=False, track=None, avoid=None):
         """Score C candidate action sequences from the envs' current state without
         stepping them (QuadSwarm.score): `actions` is a (n, C, E, D, A) device
         tensor.  Returns (ret (C, E) float64, first_done (C, E) int32): candidate
@@ -206,7 +206,9 @@ class SwarmVecEnv(VecEnv):
         (QuadSwarm.score's ret_agent).  track: a `track_spec(...)` result: also, last
         of all, cost_agent (C, E, D) float64, each drone's tracking cost against the
         spec's reference over the same steps (QuadSwarm.score's cost_agent); the
-        other results are the bytes they are without.  One launch, no host sync;
+        other results are the bytes they are without.  avoid: an `avoid_spec(...)`
+        result, with or without track: cost_agent, last of all as with track, also
+        holds the separation and obstacle terms (QuadSwarm.score's avoid).  One launch, no host sync;
         the episode log, the counters and the state are untouched.  The buffers
         are allocated once per shape and returned again by every later call of
         that shape."""
@@ -214,7 +216,8 @@ class SwarmVecEnv(VecEnv):
         if actions.dim() != 5:
             raise ValueError(f"actions must be a (n, C, {sw.num_envs}, {sw.num_drones}, {sw.act_dim}) tensor")
         n, C = actions.shape[0], actions.shape[1]
-        key = (n, C, bool(per_step), bool(per_drone), track is not None)
+        cost = track is not None or avoid is not None
+        key = (n, C, bool(per_step), bool(per_drone), cost)
         own = self._score_bufs.get(key)
         if own is None:
             kw = dict(device=sw.device)
@@ -226,20 +229,20 @@ class SwarmVecEnv(VecEnv):
                            truncated=torch.zeros((n, C, sw.num_envs), dtype=torch.uint8, **kw))
             if per_drone:
                 own.update(ret_agent=torch.zeros((C, sw.num_envs, sw.num_drones), dtype=torch.float64, **kw))
-            if track is not None:
+            if cost:
                 own.update(cost_agent=torch.zeros((C, sw.num_envs, sw.num_drones), dtype=torch.float64, **kw))
             self._score_bufs[key] = own
         outs = None
         if per_step:
             outs = [{k: own[k][j] for k in ("reward", "terminated", "truncated")} for j in range(n)]
         sw.score(actions, outs, ret=own["ret"], first_done=own["first_done"], ret_agent=own.get("ret_agent"), track=track,
-                 cost_agent=own.get("cost_agent"))
+                 cost_agent=own.get("cost_agent"), avoid=avoid)
         res = (own["ret"], own["first_done"])
         if per_step:
             res += (own["reward"], own["terminated"], own["truncated"])
         if per_drone:
             res += (own["ret_agent"],)
-        if track is not None:
+        if cost:
             res += (own["cost_agent"],)
         return res
 
